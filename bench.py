@@ -22,6 +22,11 @@ are reported separately.  --scaling weak gives every rank --nobj objects, --no-g
 the collective out.  bench.py holds no collective code of its own.
 
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the line has carried: the
+CPU baselines (unless --no-cpu), the sub-records of the default configuration (other likelihood modes, the catalogue shapes, the
+BASELINE configs the headline does not cover, the PCIe-inclusive call; unless FZ_BENCH_NO_EXTRA is set) and the check that the
+PDFs are normalised.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -133,6 +138,23 @@ def cpu_baseline_all(Y, Ye, Ym, X, Xe, Xm, z, ze, kw, budget_s):
     return {"value": rate * len(Y), "unit": "evals/s", "pdfs_per_s": rate, "cores": ncpu, "kind": "port", "cpu": cpu_model(),
             "sample": "%d objects x %d models over %d processes, ~%.0f s each (wall %.1f s incl. start-up)"
                       % (nobj, len(Y), ncpu, budget_s, wall)}
+
+
+DUMP_BYTES = 16 << 20           # per dumped array (every workload returns at most three)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each (name, device tensor) as path/<name>.npy in float64.  An array above DUMP_BYTES keeps a fixed, seeded
+    sample of its rows (sorted), the same rows on every run with the same arguments."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        n = int(t.shape[0])
+        row = 8 * (int(t[0].numel()) if t.dim() > 1 else 1)
+        if n * row > DUMP_BYTES:
+            idx = np.sort(np.random.RandomState(12345).choice(n, DUMP_BYTES // row, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64, copy=False))
 
 
 def _sub(fn):
@@ -338,6 +360,12 @@ def main():
     ap.add_argument("--exact", action="store_true", help="lprob_kwargs exact_evidence=True: every weight and the ln-evidence in fp64")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the sub-records of the default configuration and the normalisation check of the "
+                         "PDFs (without it the line's pdfs_normalised is null)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; a fixed, seeded sample of the rows of "
+                         "an array above 16 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -373,7 +401,7 @@ def main():
         ze = np.random.RandomState(78).uniform(0.01, 0.1, size=ze.shape)
     # CPU baselines first: worker processes are spawned before this process initialises the GPU
     cpu1 = cpuall = None
-    if world == 1 and not args.no_cpu and args.workload == "fit_predict" and not args.prior:
+    if args.full and world == 1 and not args.no_cpu and args.workload == "fit_predict" and not args.prior:
         cpu1 = cpu_baseline(Y, Ye, Ym, X, Xe, Xm, z, ze, kw_cpu, args.cpu_seconds)
         if (os.cpu_count() or 1) > 1:
             cpuall = cpu_baseline_all(Y, Ye, Ym, X, Xe, Xm, z, ze, kw_cpu, min(args.cpu_seconds, 10.0))
@@ -462,7 +490,7 @@ def main():
         gt = np.asarray(pd.grid, dtype=np.float64)
         kg = (gt[:, None] - gt[None, :]) / ((1. + gt[:, None]) * 0.15)          # host-side (G,G) table, pdf.py:1003-1023
         d_loss = torch.from_numpy(np.ascontiguousarray(1.0 - 1. / (1. + np.square(kg)))).to(dev)
-        d_u = torch.rand(N, dtype=torch.float64, device=dev)
+        d_u = torch.rand(N, dtype=torch.float64, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
         d_stats = torch.empty((21, N), dtype=torch.float64, device=dev)
         grid_np = np.ascontiguousarray(pd.grid, dtype=np.float64)
 
@@ -528,9 +556,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, split[0], split[1] = (float(v) for v in t.tolist())
 
+    if args.dump_outputs and rank == 0:
+        # before anything below reuses the buffers of the timed path
+        if args.workload == "fit":
+            outs = [("fit_lnprob", d_lnl), ("fit_chi2", d_chi2)]
+        elif args.workload == "summarize":
+            outs = [("summary", d_stats.t())]                  # one row of 21 statistics per object
+        elif last[0] is not None:
+            outs = [("pdfs", last[0][0]), ("lmap", last[0][1][0]), ("levid", last[0][1][1])]
+        else:
+            outs = [("pdfs", d_pdf), ("lmap", d_lm), ("levid", d_le)]
+        dump_outputs(args.dump_outputs, outs)
+
     # sanity: PDFs are normalised
     ok = True
-    if last[0] is not None:
+    if not args.full:
+        ok = None
+    elif last[0] is not None:
         d_pdf = last[0][0]
         N_chk = int(d_pdf.shape[0])
         assert N_chk == N_total
@@ -676,7 +718,7 @@ def main():
                          "avg_launch_ms": ms_launch, "evals_per_launch": evals_per_launch,
                          "modec_iterations_per_step": (tm["n_modec"] / args.steps - 2) if fam == "modec" else None},   # minus the two timed scopes (iteration driver, final pass)
         }
-        if world == 1 and args.mode == "A" and args.model_err == "const" and not args.prior and args.mask_frac == 0 and args.model_mask_frac == 0 \
+        if args.full and world == 1 and args.mode == "A" and args.model_err == "const" and not args.prior and args.mask_frac == 0 and args.model_mask_frac == 0 \
                 and args.kde == "dict" and args.label_err == "const" and args.noise_scale == 1.0 and not exact \
                 and not os.environ.get("FZ_BENCH_NO_EXTRA"):
             # the headline configuration has band-constant model errors (the easy case of mode A): the same workload (a) on the GENERAL

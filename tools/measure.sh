@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 export FZ_BENCH_NO_EXTRA=1
 O=gpurun_out
 mkdir -p $O
-FZ_BENCH_NO_EXTRA= python3 bench.py > $O/m_bench_fit_predict_modeA.json 2> $O/m_bench_fit_predict_modeA.err
+FZ_BENCH_NO_EXTRA= python3 bench.py --full > $O/m_bench_fit_predict_modeA.json 2> $O/m_bench_fit_predict_modeA.err
 python3 bench.py --exact --no-cpu > $O/m_bench_fit_predict_modeA_exact_evidence.json 2>/dev/null
 FZ_HIST=0 python3 bench.py --no-cpu > $O/m_bench_fit_predict_modeA_k_fused_round2_kernel.json 2>/dev/null
 python3 bench.py --noise-scale 3 --nobj 262144 --no-cpu > $O/m_bench_fit_predict_noise3.json 2>/dev/null
@@ -38,7 +38,7 @@ python3 bench.py --workload predict --nobj 200000 --nmodel 5000 --no-cpu --steps
 python3 bench.py --workload predict --nobj 50000 --nmodel 20000 --no-cpu --steps 5 > $O/m_bench_predict_planes_20000_models.json 2>/dev/null
 FZ_PLANE_ROWS=0 python3 bench.py --workload predict --nobj 100000 --nmodel 10000 --no-cpu --steps 5 > $O/m_bench_predict_planes_k_plane_fused.json 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_headline -- python3 bench.py --no-cpu --steps 3 --warmup 1 > $O/m_stats_headline.log 2>&1
-FZ_BENCH_NO_EXTRA= rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_default_line -- python3 bench.py --no-cpu > $O/m_stats_default_line.log 2>&1
+FZ_BENCH_NO_EXTRA= rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_default_line -- python3 bench.py --full --no-cpu > $O/m_stats_default_line.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_summarize -- python3 bench.py --workload summarize --nobj 1000000 --no-cpu --steps 3 --warmup 1 > $O/m_stats_summarize.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_planes -- python3 bench.py --workload fit --nobj 100000 --nmodel 10000 --no-cpu --steps 5 --warmup 1 > $O/m_stats_planes.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/m_stats_predict -- python3 bench.py --workload predict --nobj 100000 --nmodel 10000 --no-cpu --steps 5 --warmup 1 > $O/m_stats_predict.log 2>&1

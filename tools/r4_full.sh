@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${OUT:-r4full}; mkdir -p $O
 PYTHONUNBUFFERED=1 timeout -k 10 900 python -m pytest tests -m gpu -q -x > $O/gputest.log 2>&1; echo "pytest rc=$?"; tail -12 $O/gputest.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-python3 bench.py --steps 5 --warmup 2 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+python3 bench.py --full --steps 5 --warmup 2 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python3 -c "
 import json; d=json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1])
 print('value %.4g %s  ms/step %.2f  frac %.3f form %s cpu %.3g' % (d['value'], d['unit'], d['ms_per_step'], d['roofline']['frac'], d['config']['kernel_form'], d['cpu_baseline']['value']))

@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 TAG=${TAG:-r5_v1}
 O=gpurun_out/$TAG; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -- python3 bench.py --no-cpu --steps 3 --warmup 1 > $O/bench_default_line.json 2> $O/bench_default_line.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -- python3 bench.py --full --no-cpu --steps 3 --warmup 1 > $O/bench_default_line.json 2> $O/bench_default_line.err
 f=$(find $O/stats_default -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${TAG}_kernel_stats_default_line.csv
 echo "stats done"
 TAG=${TAG}_headline tools/pmc.sh > /dev/null 2>&1; echo "pmc headline done"
