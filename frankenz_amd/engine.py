@@ -349,6 +349,14 @@ class Engine(object):
         check(self.lib.fz_net_stack(self.h, ptr(lnprob), ptr(nsel), ptr(sel), n, nn, ptr(match), ptr(node_pdfs), node_pdfs.shape[0],
                                     node_pdfs.shape[1], ptr(pdfs), ptr(lmap), ptr(levid)))
 
+    def som_train(self, x, xe, xm, nodes, pos, draws, lr, sig, kind, use_wt, wt_thresh, cdf_thresh, opts, track_scale, s0, s1, bmus):
+        """steps [s0, s1) of SOM training (fz_som_train); arrays are NumPy or torch tensors on this engine's GPU"""
+        M, B = x.shape
+        nn, npj = pos.shape
+        check(self.lib.fz_som_train(self.h, ptr(x), ptr(xe), ptr(xm), int(M), int(B), ptr(nodes), ptr(pos), int(nn), int(npj),
+                                    ptr(draws), ptr(lr), ptr(sig), int(len(draws)), int(kind), int(bool(use_wt)), float(wt_thresh),
+                                    float(cdf_thresh), C.byref(opts), int(bool(track_scale)), int(s0), int(s1), ptr(bmus)))
+
     def pdfs_summarize(self, pdfs, pgrid, renormalize, urand, loss, widths, wscale, stats, n=None):
         n = len(pdfs) if n is None else n
         check(self.lib.fz_pdfs_summarize(self.h, ptr(pdfs), n, len(pgrid), ptr(pgrid), int(bool(renormalize)),

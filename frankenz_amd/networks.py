@@ -1,6 +1,7 @@
 """
-Inference through a trained network (SOM / GNG): the reference's ``_Network`` without its training (frankenz/networks.py:120-1473,
-SURVEY 8f-4).  The network is DATA here -- node positions in data space -- and everything the reference then does with it runs
+Inference through a trained network (SOM / GNG): the reference's ``_Network`` (frankenz/networks.py:120-1473), and
+the training of a ``SelfOrganizingMap`` on the device (networks.py:1490-1867, ``fz_som_train``, docs/som.md, at the end of this file).
+The network is DATA here -- node positions in data space -- and everything the reference then does with it runs
 through the library:
 
 * ``populate_network`` (networks.py:244-356): (Nmodel, Nnode) likelihoods with the nodes as noiseless models (``k_planes``), the
@@ -22,7 +23,8 @@ import numpy as np
 from . import pdf as _pdf
 from .engine import HostObjects, get_engine, kde_opts, like_opts, merge_kde_args
 
-__all__ = ["populate_network", "Network"]
+__all__ = ["populate_network", "Network", "SelfOrganizingMap", "learn_linear", "learn_geometric", "learn_harmonic",
+           "neighbor_gauss", "neighbor_lorentz"]
 
 _NET_CHUNK = 1 << 16          # objects per device call
 
@@ -473,3 +475,247 @@ class Network(object):
         for r in self._run(data, data_err, data_mask, lprob_func, node_pdfs is not None, wt_thresh, cdf_thresh, lprob_args, lprob_kwargs,
                            track_scale, discrete, save_fits, (model_labels, model_label_errs, label_dict, label_grid, kde_args, kde_kwargs)):
             yield r[3], r[4]
+
+
+# ---- training of a self-organizing map (reference networks.py:38-118, 1490-1867) ----------------------------------------------------
+# The schedules and neighbourhoods below keep the reference's signatures and arithmetic (the kernel is tested against its runs bit
+# for bit).  The device path recognises them by identity, as _is_default does for logprob, and tabulates the learning rate and the
+# sigma of every step up front; other callables go through _som_host_steps.
+
+def learn_linear(t, start=0.5, end=0.1, *args, **kwargs):
+    """Learning rate at run fraction ``t`` in [0, 1]: a straight line from ``start`` to ``end``."""
+    return (1. - t) * start + t * end
+
+
+def learn_geometric(t, start=0.5, end=0.1, *args, **kwargs):
+    """Learning rate at run fraction ``t``: from ``start`` to ``end`` by a constant ratio (linear in the logarithm)."""
+    return np.exp((1. - t) * np.log(start) + t * np.log(end))
+
+
+def learn_harmonic(t, start=0.5, end=0.1, *args, **kwargs):
+    """Learning rate at run fraction ``t``: its reciprocal runs linearly from 1 / ``start`` to 1 / ``end``."""
+    return 1. / ((1. - t) / start + t / end)
+
+
+_LEARN_RATES = {'linear': learn_linear, 'geometric': learn_geometric, 'harmonic': learn_harmonic}
+
+
+def _schedule(rate):
+    if rate not in _LEARN_RATES:
+        raise ValueError("Provided `rate` is not supported.")
+    return _LEARN_RATES[rate]
+
+
+def neighbor_gauss(t, pos, positions, nside, start=0.7, end=0.02, rate='harmonic', *args, **kwargs):
+    """Weights of the grid ``positions`` around ``pos``: a Gaussian in grid distance whose width runs from ``start * nside`` to
+    ``end * nside`` on the ``rate`` schedule (``nside`` None: a square grid is assumed).  Returns ``(weights, sigma)``."""
+    schedule = _schedule(rate)
+    side = np.sqrt(len(positions)) if nside is None else nside
+    d2 = np.sum((pos - positions)**2, axis=1)
+    sigma = schedule(t, start=start, end=end) * side
+    return np.exp(-0.5 * d2 / sigma**2), sigma
+
+
+def neighbor_lorentz(t, pos, positions, nside, start=0.7, end=0.02, rate='harmonic', *args, **kwargs):
+    """As ``neighbor_gauss`` with a Lorentzian profile, sigma^2 / (d^2 + sigma^2).  Returns ``(weights, sigma)``."""
+    schedule = _schedule(rate)
+    d2 = np.sum((pos - positions)**2, axis=1)
+    sigma = schedule(t, start=start, end=end) * nside
+    return sigma**2 / (d2 + sigma**2), sigma
+
+
+def som_nodes_pos(nside, nproj):
+    """(nside**nproj, nproj) float grid coordinates: coordinate i of node n is digit i of n written in base nside, most
+    significant digit first (the layout of the reference's networks.py:1804-1810)."""
+    n = np.arange(nside**nproj)
+    return np.stack([(n // nside**(nproj - 1 - i)) % nside for i in range(nproj)], axis=1).astype(np.float64)
+
+
+def _som_selection(w, wt_thresh, cdf_thresh):
+    """indices of the nodes one step moves: weights above ``wt_thresh`` of the largest, or (``wt_thresh`` None) the smallest
+    weights, taken in ascending order while their normalised running sum stays within 1 - ``cdf_thresh``"""
+    if wt_thresh is not None:
+        return np.flatnonzero(w > wt_thresh * np.max(w))
+    order = np.argsort(w)
+    running = np.cumsum((w / np.sum(w))[order])
+    return order[running <= 1. - cdf_thresh]
+
+
+_SOM_SEGMENT = 10000          # training steps per kernel launch (the map stays on the device between launches)
+
+
+def _learn_table(func, times, args, kwargs):
+    """func(t, *args, **kwargs) for every t.  The +-*/ forms give the same numbers on the whole array; anything else (np.exp / np.log
+    in learn_geometric, the user's callable) is called per t."""
+    if func is learn_linear or func is learn_harmonic:
+        return np.broadcast_to(np.asarray(func(times, *args, **kwargs), dtype=np.float64), times.shape).copy()
+    return np.array([func(t, *args, **kwargs) for t in times], dtype=np.float64)
+
+
+def _sigma_table(func, times, nside, args, kwargs):
+    """the sigma neighbor_gauss / neighbor_lorentz returns at every t"""
+    import inspect
+    b = inspect.signature(func).bind(0., None, None, nside, *args, **kwargs)
+    b.apply_defaults()
+    schedule = _schedule(b.arguments['rate'])
+    return _learn_table(schedule, times, (), {'start': b.arguments['start'], 'end': b.arguments['end']}) * nside
+
+
+def _draw_stream(rstate, nmodel, T):
+    """the rows rstate.choice(Nmodel) draws at each of T steps: for the legacy RandomState one randint call of size T is the same
+    stream; any other generator is asked T times"""
+    if rstate is np.random or isinstance(rstate, np.random.RandomState):
+        return np.ascontiguousarray(rstate.randint(0, nmodel, size=T), dtype=np.int64)
+    return np.array([rstate.choice(nmodel) for _ in range(T)], dtype=np.int64)
+
+
+def _clean_rows(x, xe, xm, rows):
+    """pdf.py:309-311 on the given rows of the arrays, in place"""
+    if not len(rows):
+        return
+    cx, ce = np.asarray(x[rows], dtype=np.float64), np.asarray(xe[rows], dtype=np.float64)
+    bad = ~(np.isfinite(cx) & np.isfinite(ce) & (ce > 0.))
+    if not bad.any():
+        return
+    sel = np.zeros(np.shape(x), dtype=bool)
+    sel[rows] = bad
+    x[sel], xe[sel], xm[sel] = 0., 1., False
+
+
+def _given(value, default):
+    return default if value is None else value
+
+
+class SelfOrganizingMap(Network):
+    """The reference's ``SelfOrganizingMap``: ``train_network`` runs on the device (``fz_som_train``, one persistent workgroup per
+    map, docs/som.md); inference is the inherited ``Network``."""
+
+    def __init__(self, models, models_err, models_mask, device=None):
+        super(SelfOrganizingMap, self).__init__(models, models_err, models_mask, device=device)
+
+    def train_network(self, models=None, models_err=None, models_mask=None, nside=50, nproj=2, nodes_init=None, niter=2000,
+                      nbatch=50, err_kernel=None, lprob_func=None, learn_func=None, neighbor_func=None, wt_thresh=1e-3,
+                      cdf_thresh=2e-4, rstate=None, lprob_args=None, lprob_kwargs=None, track_scale=False, learn_args=None,
+                      learn_kwargs=None, neighbor_args=None, neighbor_kwargs=None, verbose=True):
+        """Fit ``nside**nproj`` nodes on an ``nproj``-dimensional grid to the models (by default the ones the map was built with)
+        over ``niter * nbatch`` steps.  Keywords and defaults are the reference's (networks.py:1517-1681); afterwards ``nodes``,
+        ``nodes_pos``, ``NSIDE``, ``NNODE``, ``NPROJ``, ``NITER`` and ``NBATCH`` hold the trained map."""
+        models = _given(models, self.models)
+        models_err = _given(models_err, self.models_err)
+        models_mask = _given(models_mask, self.models_mask)
+        if err_kernel is not None:
+            models_err = np.sqrt(models_err**2 + err_kernel**2)          # added in quadrature
+        steps = self._train_network(models, models_err, models_mask, lprob_func=lprob_func, nside=nside, nproj=nproj,
+                                    nodes_init=nodes_init, learn_func=learn_func, neighbor_func=neighbor_func, niter=niter,
+                                    nbatch=nbatch, wt_thresh=wt_thresh, cdf_thresh=cdf_thresh, rstate=rstate, lprob_args=lprob_args,
+                                    lprob_kwargs=lprob_kwargs, track_scale=track_scale, learn_args=learn_args,
+                                    learn_kwargs=learn_kwargs, neighbor_args=neighbor_args, neighbor_kwargs=neighbor_kwargs)
+        for step, (_, _, rate, width) in enumerate(steps):
+            if verbose and step % nbatch == 0:                            # once per batch, the reference's progress line
+                sys.stderr.write('\rIteration %d/%d [learn=%6.3f, sigma=%6.3f]     ' % (step // nbatch + 1, niter, rate, width))
+                sys.stderr.flush()
+        if verbose:
+            sys.stderr.write('\n')
+            sys.stderr.flush()
+
+    def _train_network(self, models, models_err, models_mask, lprob_func=None, nside=50, nproj=2, nodes_init=None, learn_func=None,
+                       neighbor_func=None, niter=2000, nbatch=50, wt_thresh=1e-3, cdf_thresh=2e-4, rstate=None, lprob_args=None,
+                       lprob_kwargs=None, track_scale=False, learn_args=None, learn_kwargs=None, neighbor_args=None,
+                       neighbor_kwargs=None):
+        """Generator of the training steps, ``(node_results, bmu, learn_rate, learn_sigma)`` each.  On the device path
+        ``node_results`` is None: the (T, Nnode) likelihood rows are never formed (docs/deviations.md)."""
+        lprob_func = _given(lprob_func, _pdf.logprob)
+        lprob_args = _given(lprob_args, [])
+        lprob_kwargs = _given(lprob_kwargs, {'free_scale': True, 'ignore_model_err': True})
+        learn_func, learn_args, learn_kwargs = _given(learn_func, learn_harmonic), _given(learn_args, []), _given(learn_kwargs, {})
+        neighbor_func = _given(neighbor_func, neighbor_gauss)
+        neighbor_args, neighbor_kwargs = _given(neighbor_args, []), _given(neighbor_kwargs, {})
+        rstate = _given(rstate, np.random)
+        if wt_thresh is None and cdf_thresh is None:
+            wt_thresh = -np.inf                                           # no thresholding at all
+        T = niter * nbatch
+        times = np.linspace(0., 1., T)
+        self.NITER, self.NBATCH = niter, nbatch
+        self.NSIDE, self.NNODE, self.NPROJ = nside, nside**nproj, nproj
+        self.nodes_pos = som_nodes_pos(nside, nproj)
+        # initial nodes: distinct model rows as they stand (before any cleaning), or nodes_init itself, which is then trained in place
+        Nmodel = len(models)
+        self.nodes = np.array(models[rstate.choice(Nmodel, size=self.NNODE, replace=False)]) if nodes_init is None else nodes_init
+
+        if not (_is_default(lprob_func) and not lprob_args and neighbor_func in (neighbor_gauss, neighbor_lorentz)):
+            for step in self._som_host_steps(models, models_err, models_mask, times, rstate, lprob_func, lprob_args, lprob_kwargs,
+                                             learn_func, learn_args, learn_kwargs, neighbor_func, neighbor_args, neighbor_kwargs,
+                                             wt_thresh, cdf_thresh, track_scale):
+                yield step
+            return
+
+        opts = like_opts(lprob_kwargs)
+        if track_scale and not (opts.free_scale and lprob_kwargs.get('return_scale', False)):
+            raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True, return_scale=True)")
+        # the tables of the whole run: draws (rstate.choice per step), learning rates, sigmas
+        draws = _draw_stream(rstate, Nmodel, T)
+        lr = _learn_table(learn_func, times, learn_args, learn_kwargs)
+        sig = _sigma_table(neighbor_func, times, self.NSIDE, neighbor_args, neighbor_kwargs)
+        # the models cleaned up front (pdf.py:309-311); the reference cleans every drawn row of the caller's arrays in place, and so
+        # do we, once, before the run
+        x, xe = np.array(models, dtype=np.float64, order='C'), np.array(models_err, dtype=np.float64, order='C')
+        xm = np.array(models_mask, dtype=np.float64, order='C')
+        _clean_rows(x, xe, xm, np.arange(Nmodel))
+        _clean_rows(models, models_err, models_mask, np.unique(draws))
+        nodes = np.array(self.nodes, dtype=np.float64, order='C')
+        if nodes.shape != (self.NNODE, x.shape[1]):
+            raise ValueError("nodes_init must have shape (nside**nproj, Nfilt) = %r" % ((self.NNODE, x.shape[1]),))
+        pos = np.ascontiguousarray(self.nodes_pos, dtype=np.int32)
+        bmus = np.zeros(T, dtype=np.int32)
+        eng = self._eng()
+        kind = 0 if neighbor_func is neighbor_gauss else 1
+        use_wt = wt_thresh is not None
+        dev = _som_device_arrays(eng.device, (x, xe, xm, nodes, pos, draws, lr, sig, bmus))
+        dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, dbmus = dev
+        seg = max(1, int(_SOM_SEGMENT))
+        for s0 in range(0, T, seg):
+            s1 = min(T, s0 + seg)
+            eng.som_train(dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, kind, use_wt, wt_thresh if use_wt else 0.,
+                          0.5 if use_wt else cdf_thresh, opts, track_scale, s0, s1, dbmus)
+            if dnodes is not nodes:
+                nodes[...] = dnodes.cpu().numpy()
+                bmus[s0:s1] = dbmus[s0:s1].cpu().numpy()
+            if nodes_init is not None and isinstance(nodes_init, np.ndarray):
+                nodes_init[...] = nodes                  # the reference trains nodes_init itself
+                self.nodes = nodes_init
+            else:
+                self.nodes = nodes.copy()
+            for i in range(s0, s1):
+                yield None, int(bmus[i]), lr[i], sig[i]
+
+    def _som_host_steps(self, models, models_err, models_mask, times, rstate, lprob_func, lprob_args, lprob_kwargs, learn_func,
+                        learn_args, learn_kwargs, neighbor_func, neighbor_args, neighbor_kwargs, wt_thresh, cdf_thresh, track_scale):
+        """The training steps with the user's callables, called with the arguments the reference passes them: one drawn model
+        against the nodes as noiseless, unmasked models, then the schedule and the neighbourhood of the best node.  The map
+        (``self.nodes``) is updated in place; the drawn row is read again after the likelihood call, which may clean it."""
+        nodes, grid = self.nodes, self.nodes_pos
+        noiseless, unmasked = np.zeros_like(nodes), np.ones_like(nodes, dtype='bool')
+        for t in times:
+            row = rstate.choice(len(models))
+            fits = lprob_func(models[row], models_err[row], models_mask[row], nodes, noiseless, unmasked, *lprob_args, **lprob_kwargs)
+            if track_scale:
+                nodes *= fits[5][:, None]                                 # rescaled after the fit, before the update
+            best = np.argmax(fits[2])
+            rate = learn_func(t, *learn_args, **learn_kwargs)
+            wts, width = neighbor_func(t, grid[best], grid, self.NSIDE, *neighbor_args, **neighbor_kwargs)
+            moved = _som_selection(wts, wt_thresh, cdf_thresh)
+            nodes[moved] += rate * wts[moved, None] * (models[row] - nodes[moved])
+            yield fits, best, rate, width
+
+
+def _som_device_arrays(device, arrays):
+    """device copies of the training arrays (torch on this engine's GPU), so that the map stays on the device between launches;
+    without torch the library stages the host arrays itself"""
+    try:
+        import torch
+        if not torch.cuda.is_available():
+            return arrays
+    except ImportError:
+        return arrays
+    d = torch.device('cuda', device)
+    return tuple(torch.from_numpy(a).to(d) for a in arrays)

@@ -277,8 +277,8 @@ int  fz_nz_assign(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const d
                   int64_t* bins, int64_t* counts);
 
 /* ---- inference through a trained network (networks.py:244-356, 782-936, 1200-1473) ----
- * The network is DATA here (node positions in data space and, after populate_network, the per-node model lists); training it
- * is out of scope.  Node ln-probabilities come from fz_fit with the (matched) nodes uploaded as noiseless, unmasked models
+ * The network is DATA here (node positions in data space and, after populate_network, the per-node model lists); a SOM is
+ * trained by fz_som_train (below).  Node ln-probabilities come from fz_fit with the (matched) nodes uploaded as noiseless, unmasked models
  * (networks.py:305-307, 874-876).  Every array may live in host or device memory.
  *
  * fz_net_select -- which nodes an object's (N, Nn) ln-probabilities select, in the reference's order (networks.py:885-896, 316-327):
@@ -304,6 +304,23 @@ int  fz_net_gather(fz_ctx* ctx, const void* plane, const int32_t* nsel, const in
 int  fz_net_stack(fz_ctx* ctx, const double* lnprob, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn,
                   const int32_t* match, const double* node_pdfs, int64_t Nnodes, int64_t G, double* pdfs, double* lmap,
                   double* levid);
+
+/* ---- training of a self-organizing map (networks.py:1517-1867, SelfOrganizingMap.train_network) ----
+ * fz_som_train -- steps [s0, s1) of the sequential training loop, run by ONE persistent workgroup (docs/som.md).  Step i draws
+ * row draws[i] of the CLEANED models (M, B) / models_err / models_mask (pdf.py:309-311 applied by the caller), takes its
+ * ln-probability against every node as a noiseless, unmasked model with the likelihood options *opts (free_scale, ignore_model_err,
+ * dim_prior), rescales every node by its best-fit scale if track_scale (needs free_scale; networks.py:1838-1840), takes the
+ * best-matching unit (np.argmax order: first maximum, first nan) into bmus[i], weighs every node by its squared grid distance d to
+ * it (nodes_pos (NNODE, NPROJ) int32; neighbor_kind 0: exp(-0.5 d / sigma[i]^2), 1: sigma[i]^2 / (d + sigma[i]^2)), selects the
+ * nodes (use_wt != 0: w > wt_thresh * max(w); use_wt == 0: the ascending-weight prefix whose running probability stays
+ * <= 1 - cdf_thresh, ties split in node-index order) and moves them: nodes[n] += learn_rate[i] * w[n] * (models[row] - nodes[n])
+ * over all B bands.  nodes (NNODE, B) is read and written; draws / learn_rate / sigma / bmus have T entries.  Calling with
+ * consecutive ranges gives bit-identical nodes to one call over their union.  B <= 32, NPROJ <= 8, NNODE <= 4194304. */
+int  fz_som_train(fz_ctx* ctx, const double* models, const double* models_err, const double* models_mask, int64_t M, int32_t B,
+                  double* nodes, const int32_t* nodes_pos, int32_t NNODE, int32_t NPROJ, const int64_t* draws,
+                  const double* learn_rate, const double* sigma, int64_t T, int32_t neighbor_kind, int32_t use_wt,
+                  double wt_thresh, double cdf_thresh, const fz_like_opts* opts, int32_t track_scale, int64_t s0, int64_t s1,
+                  int32_t* bmus);
 
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
