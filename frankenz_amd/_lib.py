@@ -91,6 +91,13 @@ ABI = {
     "fz_pdfs_resample": (C.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _F64, _F64, _I32, _P]),
     "fz_overlap_nz": (C.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _F64, _P, _P]),
     "fz_nz_assign": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "fz_dev_alloc": (C.c_int, [_P, _I64, C.POINTER(_P)]),
+    "fz_dev_free": (C.c_int, [_P, _P]),
+    "fz_dev_copy": (C.c_int, [_P, _P, _P, _I64]),
+    "fz_pdfs_colsum": (C.c_int, [_P, _P, _I64, _I64, _P]),
+    "fz_nz_pairs": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _P, _P, _P, _P]),
+    "fz_nz_pair_eval": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I64, _I64, _I32, _F64, _F64, _P]),
+    "fz_nz_sweep": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, C.c_uint32, C.c_uint32, C.c_uint64, _P]),
     "fz_net_select": (C.c_int, [_P, _P, _I64, _I32, _I32, _F64, _F64, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "fz_net_table": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _I64, _P]),
     "fz_net_gather": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, C.c_uint64, _P]),

@@ -13,6 +13,7 @@
 #include "fz_summary.h"
 #include "fz_net.h"
 #include "fz_som.h"
+#include "fz_nzmc.h"
 
 using namespace fz;
 
@@ -1174,6 +1175,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_summary_host.inc"
 #include "fz_net_host.inc"
 #include "fz_som_host.inc"
+#include "fz_nzmc_host.inc"
 
 #ifdef FZ_KM_STATS
 extern "C" int fz_debug_kmstats(unsigned long long* out, int reset) {

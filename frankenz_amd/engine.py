@@ -378,6 +378,44 @@ class Engine(object):
         check(self.lib.fz_overlap_nz(self.h, ptr(pdfs), n, len(nz), ptr(nz), pi, pj, float(step), ptr(overlap), ptr(out)))
         return float(out[0])
 
+    # -- the n(z) samplers (samplers.py; fz_nzmc.h) ---------------------------
+    def device_empty(self, shape, dtype=np.float64):
+        """an uninitialised array in this engine's device memory that lives until its last reference dies (``DeviceArray``)"""
+        return DeviceArray(self, shape, dtype)
+
+    def device_array(self, a):
+        """``a`` (NumPy) copied into device memory"""
+        a = np.ascontiguousarray(a)
+        d = DeviceArray(self, a.shape, a.dtype)
+        d.set_rows(0, a)
+        return d
+
+    def pdfs_colsum(self, pdfs, G, out, n=None):
+        n = len(pdfs) if n is None else n
+        check(self.lib.fz_pdfs_colsum(self.h, ptr(pdfs), n, int(G), ptr(out)))
+
+    def nz_pairs(self, pdfs, n, G, pos, overlap, dcol, lnpost, pairs, normals, expo, nsamp, thin, mh_steps, s0, s1, samples,
+                 samples_lnp, accept, gscale):
+        """saved samples [s0, s1) of the population chain (fz_nz_pairs); pdfs, overlap and dcol live on this engine's GPU"""
+        check(self.lib.fz_nz_pairs(self.h, ptr(pdfs), int(n), int(G), ptr(pos), ptr(overlap), ptr(dcol), ptr(lnpost), ptr(pairs),
+                                   ptr(normals), ptr(expo), int(nsamp), int(thin), int(mh_steps), int(s0), int(s1), ptr(samples),
+                                   ptr(samples_lnp), ptr(accept), ptr(gscale)))
+
+    def nz_pair_eval(self, pdfs, n, G, overlap, dcol, what, pair, pend, step):
+        """one evaluation of the population chain for a host-side decision (fz_nz_pair_eval); ``pend``: the accepted step not yet
+        applied, or None.  Returns the two sums."""
+        sums = np.zeros(2)
+        pi, pj = (-1, -1) if pair is None else (int(pair[0]), int(pair[1]))
+        check(self.lib.fz_nz_pair_eval(self.h, ptr(pdfs), int(n), int(G), ptr(overlap), ptr(dcol), int(what), pi, pj,
+                                       int(pend is not None), 0. if pend is None else float(pend), float(step), ptr(sums)))
+        return sums
+
+    def nz_sweep(self, pdfs, n, nz, counts, u=None, key=None, sweep=0):
+        """counts of one Gibbs sweep's categorical draws (fz_nz_sweep): the caller's uniforms ``u``, or Philox under ``key``"""
+        k0, k1 = (0, 0) if key is None else (int(key[0]), int(key[1]))
+        check(self.lib.fz_nz_sweep(self.h, ptr(pdfs), int(n), len(nz), ptr(nz), ptr(u), int(key is not None), k0, k1, int(sweep),
+                                   ptr(counts)))
+
     def knn_search_fit_predict(self, q, x, xe, xm, k, lp_norm, distance_upper_bound, opts, kopts, prior=None,
                                neighbors=None, nnbr=None, lnprior=None, lnlike=None, lnprob=None, chi2=None, ndim=None,
                                scale=None, scale_err=None, pdfs=None, lmap=None, levid=None, n=None):
@@ -436,6 +474,45 @@ class Engine(object):
 
     def set_workspace_limit(self, nbytes):
         check(self.lib.fz_set_workspace_limit(self.h, int(nbytes)))
+
+
+class DeviceArray(object):
+    """A C-contiguous array in an engine's device memory (fz_dev_alloc), with the few tensor-like members the host layer looks at
+    (``shape``, ``data_ptr()``, ``len()``); ``numpy()`` copies it to the host, ``set_rows(r0, a)`` copies ``a`` in at row ``r0``."""
+
+    def __init__(self, eng, shape, dtype=np.float64):
+        self.shape = tuple(int(v) for v in np.atleast_1d(shape))
+        self.dtype = np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        self._eng, self._ptr = eng, None
+        h = C.c_void_p()
+        check(eng.lib.fz_dev_alloc(eng.h, self.nbytes, C.byref(h)))
+        self._ptr = h.value
+
+    def data_ptr(self):
+        return self._ptr
+
+    def __len__(self):
+        return self.shape[0]
+
+    def numpy(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        check(self._eng.lib.fz_dev_copy(self._eng.h, ptr(out), self._ptr, self.nbytes))
+        return out
+
+    def set_rows(self, r0, a):
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        row = self.dtype.itemsize * int(np.prod(self.shape[1:], dtype=np.int64))
+        if a.shape[1:] != self.shape[1:] or r0 < 0 or r0 + len(a) > self.shape[0]:
+            raise ValueError("rows [%d, %d) do not fit an array of shape %r" % (r0, r0 + len(a), self.shape))
+        check(self._eng.lib.fz_dev_copy(self._eng.h, self._ptr + r0 * row, ptr(a), a.nbytes))
+
+    def __del__(self):
+        try:
+            if self._ptr and getattr(self._eng, "h", None):
+                self._eng.lib.fz_dev_free(self._eng.h, self._ptr)
+        except Exception:           # interpreter shutdown
+            pass
 
 
 _engines = {}

@@ -322,6 +322,45 @@ int  fz_som_train(fz_ctx* ctx, const double* models, const double* models_err, c
                   double wt_thresh, double cdf_thresh, const fz_like_opts* opts, int32_t track_scale, int64_t s0, int64_t s1,
                   int32_t* bmus);
 
+/* ---- device memory that outlives a call (the samplers' resident PDF stack and per-object state) ----
+ * fz_dev_alloc / fz_dev_free: plain device allocations on the context's GPU.  fz_dev_copy: `bytes` from src to dst, either side in
+ * host or device memory, complete on return. */
+int  fz_dev_alloc(fz_ctx* ctx, int64_t bytes, void** out);
+int  fz_dev_free(fz_ctx* ctx, void* p);
+int  fz_dev_copy(fz_ctx* ctx, void* dst, const void* src, int64_t bytes);
+
+/* ---- the n(z) samplers (samplers.py:83-535: population_sampler, hierarchical_sampler; docs/samplers.md) ----
+ * fz_pdfs_colsum -- colsum (G) = pdfs.sum(axis=0) in a fixed order (blocks of 512 rows added in row order, then the blocks in
+ * order): the stacked n(z), and with it the samplers' default start  colsum / sum(colsum). */
+int  fz_pdfs_colsum(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, double* colsum);
+/* fz_nz_pairs -- saved samples [s0, s1) of population_sampler.sample (samplers.py:262-308) with a flat prior, `thin` pairs per
+ * sample and mh_steps proposals per pair, without a host synchronisation in between.  pdfs (N, G), overlap (N) = pdfs @ pos and the
+ * scratch column dcol (N) must be DEVICE arrays; pos (G) and lnpost (1) are read and written; pairs (nsamp * thin, 2) int64,
+ * normals and expo (nsamp * thin, mh_steps) are the reference's random stream drawn ahead (rstate.choice(G, 2, replace=False) per
+ * pair at the start of each sample, then per proposal randn() and exponential()).  Per pair (i, j), d = pdfs[:, i] - pdfs[:, j]:
+ * scale = 1e-4 min(pos[i], pos[j], 1 - pos[i], 1 - pos[j]); grad = (sum log(overlap + scale/2 d) - sum log(overlap - scale/2 d)) /
+ * scale; gscale = min(|1 / grad|, |scale 1e4|) (|scale| if grad == 0); per proposal z = normal * gscale, rejected without an
+ * evaluation if pos[i] + z or pos[j] - z is negative or not finite, accepted if -expo < sum log(overlap + z d) - lnpost, and then
+ * overlap += z d, pos[i] += z, pos[j] -= z.  Every sum is formed in one fixed order (blocks of 1024 objects, then the block sums in
+ * index order): a chain is reproducible bit for bit, also when cut into segments.  Out: samples (nsamp, G), samples_lnp (nsamp) rows
+ * [s0, s1); accept (nsamp * thin, mh_steps) int32 and gscale (nsamp * thin) of the segment's pairs. */
+int  fz_nz_pairs(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, double* pos, double* overlap, double* dcol, double* lnpost,
+                 const int64_t* pairs, const double* normals, const double* expo, int64_t nsamp, int32_t thin, int32_t mh_steps,
+                 int64_t s0, int64_t s1, double* samples, double* samples_lnp, int32_t* accept, double* gscale);
+/* fz_nz_pair_eval -- one evaluation of the same chain with the decision left to the host (a user's ln-prior is a Python callable).
+ * An accepted step is handed back as (has_pend, pend_step) and applied to overlap (with the column in dcol) before anything else.
+ * what 0: gather dcol for the new pair (pair_i, pair_j), sums[0], sums[1] = sum log(overlap +- step * dcol); what 1: sums[0] =
+ * sum log(overlap + step * dcol); what 2: the pending step only.  sums is a host array of two doubles. */
+int  fz_nz_pair_eval(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, double* overlap, double* dcol, int32_t what,
+                     int64_t pair_i, int64_t pair_j, int32_t has_pend, double pend_step, double step, double* sums);
+/* fz_nz_sweep -- the assignment step of one Gibbs sweep of hierarchical_sampler (samplers.py:498-499, 519-520): fz_nz_assign's draw
+ * and counts (G, int64) without the per-object bins; a row without mass under nz is left out of the counts.  use_philox == 0: the
+ * uniforms u (N) of the caller.  use_philox != 0: object i draws the uniform of Philox4x32-10 under the key (key0, key1) at the
+ * counter (i lo, i hi, sweep lo, sweep hi), made of the first two output words a, b as ((a >> 5) 2^26 + (b >> 6)) / 2^53
+ * (samplers._philox_uniform is the NumPy twin). */
+int  fz_nz_sweep(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const double* nz, const double* u, int32_t use_philox,
+                 uint32_t key0, uint32_t key1, uint64_t sweep, int64_t* counts);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
