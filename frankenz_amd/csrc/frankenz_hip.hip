@@ -25,12 +25,18 @@ namespace {
 struct DbgOpts { std::mutex mu; std::vector<std::pair<std::string, std::string>> kv; };
 DbgOpts& dbg_opts() { static DbgOpts d; return d; }
 }
-const char* fz_dbg(const char* name) {
+// `use(value)` under the lock, value == nullptr when the switch is not set: the pointer dies with the lock (fz_debug_opts, which any
+// thread may call, clears the table), so the three readers hand out values only
+template <class F>
+static auto with_dbg(const char* name, F&& use) {
     DbgOpts& d = dbg_opts();
     std::lock_guard<std::mutex> lk(d.mu);
-    for (auto& e : d.kv) if (e.first == name) return e.second.c_str();      // (stable until the next fz_debug_opts)
-    return nullptr;
+    for (auto& e : d.kv) if (e.first == name) return use(e.second.c_str());
+    return use((const char*)nullptr);
 }
+bool fz_dbg_set(const char* name) { return with_dbg(name, [](const char* v) { return v != nullptr; }); }
+long long fz_dbg_int(const char* name, long long unset) { return with_dbg(name, [&](const char* v) { return v ? atoll(v) : unset; }); }
+std::string fz_dbg_str(const char* name) { return with_dbg(name, [](const char* v) { return std::string(v ? v : ""); }); }
 extern "C" int fz_debug_opts(const char* spec) {
     DbgOpts& d = dbg_opts();
     std::lock_guard<std::mutex> lk(d.mu);
@@ -191,7 +197,37 @@ __global__ void k_prep_models(const double* y, const double* ye, const double* y
     if (fl) atomicOr(flags, fl);
 }
 
-static int pick_bt(int B) { return (B >= 4 && B <= 8) ? B : (B < 4 ? 4 : (B <= 12 ? 12 : (B <= 16 ? 16 : (B <= 24 ? 24 : (B <= 32 ? 32 : 0))))); }
+// ---- what an upload makes stale ----
+// every upload starts by forgetting the share of pairs fz_nolist_probe sampled: it belongs to the previous models and labels
+static void upload_begins(fz_ctx* c) { c->probe_share = -1.0; c->probe_pending = false; }
+enum UploadKind { UP_MODELS, UP_DICT_LABELS, UP_GRID_LABELS };
+static void upload_invalidates(fz_ctx* c, UploadKind k) {
+    // the segmented layout is built from the models' masks AND the labels' classes: every upload
+    c->seg_state = 0; c->seg_rec0_valid = c->seg_rec1_valid = false;
+    // class-sorted copies of the model records: stale with new records (models) or a new permutation (dictionary labels).  Grid labels
+    // leave them alone: nothing reads them while mc_ok is false, and the next dictionary upload resets them
+    if (k != UP_GRID_LABELS) c->mc_rec0_valid = c->mc_rec1_valid = false;
+    // tables of the class-sorted stack: they belong to the labels.  A model upload leaves mc_ok alone: it sets label_mode = 0, so
+    // labels come again (and decide mc_ok) before anything reads it
+    if (k != UP_MODELS) c->mc_ok = false;
+}
+
+// the units linked into this library, in the order of FZ_BT_LIST (ascending)
+#define FZ_BT_UNIT(N) fz_bt_unit_##N,
+static const fz_bt_table* (*const bt_units[])() = {FZ_BT_LIST(FZ_BT_UNIT)};
+#undef FZ_BT_UNIT
+// band count the models are padded to: the smallest compiled one that holds B bands (0: none does)
+static int pick_bt(int B) {
+    for (auto unit : bt_units) if (unit()->BT >= B) return unit()->BT;
+    return 0;
+}
+// the entry points of the context's band count; nullptr (error set, -5 for the caller to return) when no unit was compiled for it --
+// fz_models_upload only ever sets a count pick_bt answered, so this is not reached through the ABI
+static const fz_bt_table* bt_lookup(const fz_ctx* c) {
+    for (auto unit : bt_units) if (unit()->BT == c->BT) return unit();
+    fail(-5, "no kernels are compiled for %d bands", c->BT);
+    return nullptr;
+}
 
 extern "C" int fz_models_upload(fz_ctx* c, const double* y, const double* ye, const double* ym, int64_t M, int32_t B) {
     if (!c || !y || !ye || !ym) return fail(-1, "fz_models_upload: NULL argument");
@@ -199,30 +235,27 @@ extern "C" int fz_models_upload(fz_ctx* c, const double* y, const double* ye, co
     const int BT = pick_bt(B);
     if (!BT) return fail(-5, "fz_models_upload: %d bands unsupported (max 32)", B);
     HIPCHK(hipSetDevice(c->device));
-    c->probe_share = -1.0; c->probe_pending = false;  // what was sampled belongs to the previous model set
-    const int64_t Mp = (M + FZ_MP_ALIGN - 1) / FZ_MP_ALIGN * FZ_MP_ALIGN;      // whole tiles of every kernel (fz_ctx.h)
+    upload_begins(c);
+    const int64_t Mp = fz_padded_models(M);
     const size_t raw = (size_t)M * B * sizeof(double);
     FZCHK(c->d_rx.ensure(raw)); FZCHK(c->d_rxe.ensure(raw)); FZCHK(c->d_rxm.ensure(raw));
     FZCHK(copy_in(c, c->d_rx.p, y, raw)); FZCHK(copy_in(c, c->d_rxe.p, ye, raw)); FZCHK(copy_in(c, c->d_rxm.p, ym, raw));
     FZCHK(c->d_y.ensure((size_t)BT * Mp * 8)); FZCHK(c->d_ye2.ensure((size_t)BT * Mp * 8)); FZCHK(c->d_ye.ensure((size_t)BT * Mp * 8));
-    FZCHK(c->d_mbits.ensure((size_t)Mp * 4)); FZCHK(c->d_flags.ensure(64));
+    FZCHK(c->d_mbits.ensure((size_t)Mp * 4));
     const int rw0 = fz_rec_width(2 * BT), rw1 = fz_rec_width(BT);
     FZCHK(c->d_rec0.ensure((size_t)Mp * rw0 * 8)); FZCHK(c->d_rec1.ensure((size_t)Mp * rw1 * 8));
-    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-    {
+    int fl = 0;
+    FZCHK(fz_flag_roundtrip(c, fl, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
         hipLaunchKernelGGL(k_prep_models, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_rx.as<double>(), c->d_rxe.as<double>(), c->d_rxm.as<double>(), M, Mp, (int)B, BT,
-                           c->d_y.as<double>(), c->d_ye2.as<double>(), c->d_ye.as<double>(), c->d_mbits.as<uint32_t>(), c->d_flags.as<int>(),
+                           c->d_y.as<double>(), c->d_ye2.as<double>(), c->d_ye.as<double>(), c->d_mbits.as<uint32_t>(), d_flags,
                            c->d_rec0.as<double>(), rw0, c->d_rec1.as<double>(), rw1);
-    }
-    HIPCHK(hipGetLastError());
-    int fl = 0;
-    FZCHK(copy_out(c, &fl, c->d_flags.p, sizeof fl));
+        return 0;
+    }));
     if (fl & 2) return fail(-4, "models_mask must be binary (0/1)");
     c->M = M; c->Mp = Mp; c->B = B; c->BT = BT;
-    c->mc_rec0_valid = c->mc_rec1_valid = false;
-    c->seg_state = 0; c->seg_rec0_valid = c->seg_rec1_valid = false;
+    upload_invalidates(c, UP_MODELS);
     c->h_mbits.resize((size_t)M);
     FZCHK(copy_out(c, c->h_mbits.data(), c->d_mbits.p, (size_t)M * 4));
     c->models_masked = (fl & 1) || (BT != B);
@@ -232,7 +265,7 @@ extern "C" int fz_models_upload(fz_ctx* c, const double* y, const double* ye, co
     // band-constant model errors (zeros for a template grid, a common floor, the SURVEY 8d
     // configurations): xe^2 + ye^2 does not depend on the model, so it is formed once per object
     // and mode A runs on the kernels of mode Ai (see obj_vmode); FZ_NO_ERRCONST=1 disables this
-    c->models_err_const = !(fl & 8) && !fz_dbg("FZ_NO_ERRCONST");
+    c->models_err_const = !(fl & 8) && !fz_dbg_set("FZ_NO_ERRCONST");
     {
         std::vector<double> e0(B), e2(BT, 0.0);
         FZCHK(copy_out(c, e0.data(), c->d_rxe.p, (size_t)B * 8));
@@ -275,13 +308,34 @@ extern "C" int fz_kdedict_upload(fz_ctx* c, int64_t G, int64_t D, const int64_t*
     return 0;
 }
 
+// Mass of a dictionary kernel that lands on the grid [0, G) when it is centred on grid index p: the normalisation of the edge-truncated
+// kernel, pdf.py:613-617.  cdf: the kernel's cumulative sums, len = 2 w + 1 of them; the window [p - w, p + w] must overlap the grid.
+static double edge_mass(const double* cdf, int64_t len, int64_t w, int64_t p, int64_t G) {
+    const int64_t lo = std::max<int64_t>(p - w, 0), hi = std::min<int64_t>(p + w + 1, G);
+    const int64_t lpad = lo - (p - w), hpad = hi - (p + w + 1);
+    // kcdf[hpad-1] with Python negative indexing -> element len+hpad-1
+    double mass = cdf[len + hpad - 1];
+    if (lpad != 0) mass -= cdf[lpad - 1];
+    return mass;
+}
+// ... as a table over a padded histogram row: row[q] <-> grid index q - shift, q in [0, n); entries whose window misses the grid, or
+// whose mass is not positive, keep the 1.0 the caller filled in
+static void edge_mass_row(const double* cdf, int64_t len, int64_t w, int64_t G, int64_t shift, int64_t n, double* row) {
+    for (int64_t q = 0; q < n; ++q) {
+        const int64_t p = q - shift;
+        if (p + w < 0 || p - w > G - 1) continue;
+        const double mass = edge_mass(cdf, len, w, p, G);
+        if (mass > 0.0) row[q] = mass;
+    }
+}
+
 extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int64_t* y_std_idx, int64_t M) {
     if (!c || !y_idx || !y_std_idx) return fail(-1, "fz_labels_upload_dict: NULL argument");
     if (!c->D) return fail(-1, "fz_labels_upload_dict: upload the dictionary first");
     if (M <= 0) return fail(-1, "fz_labels_upload_dict: M <= 0");
     HIPCHK(hipSetDevice(c->device));
-    c->probe_share = -1.0; c->probe_pending = false;  // what was sampled belongs to the previous model set
-    const int64_t Mp = (M + FZ_MP_ALIGN - 1) / FZ_MP_ALIGN * FZ_MP_ALIGN;      // whole tiles of every kernel (fz_ctx.h)
+    upload_begins(c);
+    const int64_t Mp = fz_padded_models(M);
     std::vector<int64_t> hy(M), hs(M);
     if (is_device_ptr(y_idx)) {
         HIPCHK(hipMemcpy(hy.data(), y_idx, M * 8, hipMemcpyDeviceToHost));
@@ -302,12 +356,7 @@ extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int6
         // window [p-w, p+w] must overlap the grid (else pdf.py:612-620 raises IndexError / shape errors)
         if (p + w < 0 || p - w > G - 1)
             return fail(-3, "label %lld: grid index %lld with kernel half-width %lld lies off the grid", (long long)j, (long long)p, (long long)w);
-        const int64_t lo = std::max<int64_t>(p - w, 0), hi = std::min<int64_t>(p + w + 1, G);
-        const int64_t lpad = lo - (p - w), hpad = hi - (p + w + 1);
-        const double* cdf = c->h_kcdf.data() + c->h_offsets[d];
-        // kcdf[hpad-1] with Python negative indexing -> element len+hpad-1   (pdf.py:613-617)
-        double mass = cdf[len + hpad - 1];
-        if (lpad != 0) mass -= cdf[lpad - 1];
+        const double mass = edge_mass(c->h_kcdf.data() + c->h_offsets[d], len, w, p, G);
         pos[j] = (int32_t)p; cls[j] = (int32_t)d; nrm[j] = mass;
         if (d != hs[0]) single = false;
     }
@@ -320,33 +369,29 @@ extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int6
         // one dictionary kernel for every label: the edge-truncated mass (pdf.py:613-617) is a function of the
         // grid index alone -- a table over the padded histogram row [0, G + 2 w0), entry q <-> index q - w0
         const int64_t d = hs[0], w = c->h_widths[d], len = c->h_offsets[d + 1] - c->h_offsets[d];
-        const double* cdf = c->h_kcdf.data() + c->h_offsets[d];
         std::vector<double> tab((size_t)(G + 2 * w), 1.0);
-        for (int64_t q = 0; q < G + 2 * w; ++q) {
-            const int64_t pp = q - w;
-            if (pp + w < 0 || pp - w > G - 1) continue;
-            const int64_t lo = std::max<int64_t>(pp - w, 0), hi = std::min<int64_t>(pp + w + 1, G);
-            const int64_t lpad = lo - (pp - w), hpad = hi - (pp + w + 1);
-            double mass = cdf[len + hpad - 1];
-            if (lpad != 0) mass -= cdf[lpad - 1];
-            tab[(size_t)q] = (mass > 0.0) ? mass : 1.0;
-        }
+        edge_mass_row(c->h_kcdf.data() + c->h_offsets[d], len, w, G, w, G + 2 * w, tab.data());
         FZCHK(c->d_normtab.ensure(tab.size() * 8));
         FZCHK(copy_in(c, c->d_normtab.p, tab.data(), tab.size() * 8));
     }
+    // (the segmented layout goes stale here too, a little before the new labels are recorded below: nothing in between reads it)
+    upload_invalidates(c, UP_DICT_LABELS);
+    // dictionary classes present, ranked in dictionary order: the class order of the stack below and of the segments (fz_segments)
+    std::vector<int32_t> rank((size_t)c->D, -1);
+    int32_t nrank = 0;
+    for (int64_t j = 0; j < M; ++j) rank[hs[j]] = 0;
+    for (int64_t d = 0; d < c->D; ++d) if (rank[d] == 0) rank[d] = nrank++;
     // many dictionary widths: tables of the class-sorted stack (k_fused MC) -- the kernel's copy of the model records
     // is ordered by class, so every object's candidate list comes out grouped by class and the PDF stage can keep ONE
     // histogram, convolved with its class's kernel whenever the class changes.  Limits: half-widths <= 63 (the taps
     // sit in two registers across the wave), G <= 768 (the result row sits in 12 registers per lane).
-    c->mc_ok = false; c->mc_rec0_valid = c->mc_rec1_valid = false;
     if (!single) {
-        std::vector<int32_t> present((size_t)c->D, 0);
         int64_t W0 = 0;
-        for (int64_t j = 0; j < M; ++j) { present[hs[j]] = 1; W0 = std::max<int64_t>(W0, c->h_widths[hs[j]]); }
+        for (int64_t j = 0; j < M; ++j) W0 = std::max<int64_t>(W0, c->h_widths[hs[j]]);
         const int64_t Gp = G + 2 * W0;
         if (W0 <= 63 && G <= 768 && Gp < 1024) {
-            std::vector<int32_t> rank((size_t)c->D, -1), rwidth; std::vector<int64_t> roff, start;
-            for (int64_t d = 0; d < c->D; ++d) if (present[d]) { rank[d] = (int32_t)rwidth.size(); rwidth.push_back((int32_t)c->h_widths[d]); roff.push_back(c->h_offsets[d]); }
+            std::vector<int32_t> rwidth; std::vector<int64_t> roff, start;
+            for (int64_t d = 0; d < c->D; ++d) if (rank[d] >= 0) { rwidth.push_back((int32_t)c->h_widths[d]); roff.push_back(c->h_offsets[d]); }
             const size_t C = rwidth.size();
             start.assign(C + 1, 0);
             for (int64_t j = 0; j < M; ++j) ++start[rank[hs[j]] + 1];
@@ -358,22 +403,11 @@ extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int6
                 perm[nj] = (int32_t)j; tag[nj] = (r << 10) | (int32_t)(hy[j] + W0);
             }
             std::vector<double> ntab(C * (size_t)Gp, 1.0);
-            size_t r = 0;
-            for (int64_t d = 0; d < c->D; ++d) {
-                if (!present[d]) continue;
-                const int64_t w = c->h_widths[d], len = c->h_offsets[d + 1] - c->h_offsets[d];
-                const double* cdf = c->h_kcdf.data() + c->h_offsets[d];
-                for (int64_t q = 0; q < Gp; ++q) {
-                    const int64_t pp = q - W0;
-                    if (pp + w < 0 || pp - w > G - 1) continue;
-                    const int64_t lo = std::max<int64_t>(pp - w, 0), hi = std::min<int64_t>(pp + w + 1, G);
-                    const int64_t lpad = lo - (pp - w), hpad = hi - (pp + w + 1);
-                    double mass = cdf[len + hpad - 1];
-                    if (lpad != 0) mass -= cdf[lpad - 1];
-                    ntab[r * Gp + q] = mass > 0.0 ? mass : 1.0;       // a zero / underflowed mass: no model of this class stacks at q (the labels were checked), the row entry stays 0
-                }
-                ++r;
-            }
+            // (a zero / underflowed mass reads 1: no model of this class stacks at q -- the labels were checked --, the row entry stays 0)
+            for (int64_t d = 0; d < c->D; ++d)
+                if (rank[d] >= 0)
+                    edge_mass_row(c->h_kcdf.data() + c->h_offsets[d], c->h_offsets[d + 1] - c->h_offsets[d], c->h_widths[d], G, W0, Gp,
+                                  ntab.data() + (size_t)rank[d] * Gp);
             FZCHK(c->d_mc_tag.ensure(Mp * 4)); FZCHK(c->d_mc_perm.ensure(M * 4)); FZCHK(c->d_mc_width.ensure(C * 4));
             FZCHK(c->d_mc_off.ensure(C * 8)); FZCHK(c->d_mc_norm.ensure(ntab.size() * 8));
             FZCHK(copy_in(c, c->d_mc_tag.p, tag.data(), Mp * 4)); FZCHK(copy_in(c, c->d_mc_perm.p, perm.data(), M * 4));
@@ -390,7 +424,7 @@ extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int6
     }
     c->label_mode = 1; c->label_M = M;
     c->h_pos.assign(pos.begin(), pos.begin() + M); c->h_cls.assign(cls.begin(), cls.begin() + M);
-    c->seg_state = 0; c->seg_rec0_valid = c->seg_rec1_valid = false;
+    c->h_rank = std::move(rank); c->n_rank = nrank;
     return 0;
 }
 
@@ -432,12 +466,10 @@ extern "C" int fz_labels_upload_grid(fz_ctx* c, const double* y, const double* y
     if (!c || !y || !ystd || !grid) return fail(-1, "fz_labels_upload_grid: NULL argument");
     if (M <= 0 || G <= 1) return fail(-1, "fz_labels_upload_grid: bad sizes");
     HIPCHK(hipSetDevice(c->device));
-    c->probe_share = -1.0; c->probe_pending = false;  // what was sampled belongs to the previous model set
-    const int64_t Mp = (M + FZ_MP_ALIGN - 1) / FZ_MP_ALIGN * FZ_MP_ALIGN;      // whole tiles of every kernel (fz_ctx.h)
+    upload_begins(c);
+    const int64_t Mp = fz_padded_models(M);
     FZCHK(c->d_ly.ensure(Mp * 8)); FZCHK(c->d_lstd.ensure(Mp * 8)); FZCHK(c->d_grid.ensure(G * 8));
     FZCHK(c->d_lo.ensure(Mp * 4)); FZCHK(c->d_hi.ensure(Mp * 4)); FZCHK(c->d_norm.ensure(Mp * 8));
-    FZCHK(c->d_flags.ensure(64));
-    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
     HIPCHK(hipMemsetAsync(c->d_lo.p, 0, Mp * 4, c->stream));
     HIPCHK(hipMemsetAsync(c->d_hi.p, 0, Mp * 4, c->stream));
     HIPCHK(hipMemsetAsync(c->d_norm.p, 0, Mp * 8, c->stream));
@@ -461,21 +493,20 @@ extern "C" int fz_labels_upload_grid(fz_ctx* c, const double* y, const double* y
     }
     FZCHK(c->d_lrec.ensure((size_t)Mp * 48));
     HIPCHK(hipMemsetAsync(c->d_lrec.p, 0, (size_t)Mp * 48, c->stream));
-    {
+    int fl = 0;
+    FZCHK(fz_flag_roundtrip(c, fl, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
         hipLaunchKernelGGL(k_prep_grid_labels, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_ly.as<double>(), c->d_lstd.as<double>(), M, c->d_grid.as<double>(), (int)G, dx,
                            sig_thresh, c->d_lo.as<int32_t>(), c->d_hi.as<int32_t>(), c->d_norm.as<double>(),
-                           c->d_flags.as<int>(), c->grid_step, c->d_lrec.as<double>());
-    }
-    HIPCHK(hipGetLastError());
-    int fl = 0;
-    FZCHK(copy_out(c, &fl, c->d_flags.p, sizeof fl));
+                           d_flags, c->grid_step, c->d_lrec.as<double>());
+        return 0;
+    }));
     if (fl & 1) return fail(-4, "gauss_kde labels: non-finite label or label error");
     if (fl & 2) return fail(-3, "gauss_kde labels: a label's window lies wholly below the grid "
                                 "(the reference's negative-index slicing there is not reproduced)");
-    c->G = G; c->label_mode = 2; c->label_M = M; c->mc_ok = false;
-    c->seg_state = 0; c->seg_rec0_valid = c->seg_rec1_valid = false;
+    c->G = G; c->label_mode = 2; c->label_M = M;
+    upload_invalidates(c, UP_GRID_LABELS);
     return 0;
 }
 
@@ -500,14 +531,9 @@ int fz_segments(fz_ctx* c, bool rec0) {
         c->seg_state = -1;
         const int64_t M = c->M;
         if (c->label_mode != 1 || c->label_M != M || (int64_t)c->h_mbits.size() != M || (int64_t)c->h_cls.size() != M) return 1;
-        // dictionary classes present, in dictionary order (the ranks of the class-sorted stack, fz_labels_upload_dict)
-        std::vector<int32_t> rank((size_t)c->D, -1);
-        int32_t C = 0;
-        {
-            std::vector<char> present((size_t)c->D, 0);
-            for (int64_t j = 0; j < M; ++j) present[c->h_cls[j]] = 1;
-            for (int64_t d = 0; d < c->D; ++d) if (present[d]) rank[d] = C++;
-        }
+        // dictionary classes present, in dictionary order (ranked by fz_labels_upload_dict: the ranks of the class-sorted stack)
+        const std::vector<int32_t>& rank = c->h_rank;
+        const int32_t C = c->n_rank;
         if (C > 1 && !c->mc_ok) return 1;                        // (tables of the class-sorted stack: half-widths <= 63, G <= 768)
         const int64_t W0 = C > 1 ? c->mc_w0 : c->w0;
         if (c->G + 2 * W0 > 65535) return 1;                     // the candidate buffers hold 16-bit label indices
@@ -645,16 +671,13 @@ static int prep_chunk(fz_ctx* c, double* x, double* xe, double* xm, int64_t i0, 
         FZCHK(c->d_ox.ensure(d)); FZCHK(c->d_ov.ensure(d));
         FZCHK(c->d_obits.ensure((size_t)n * 4)); FZCHK(c->d_oslv.ensure((size_t)n * 8));
     }
-    FZCHK(c->d_flags.ensure(64));
-    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-    {
+    FZCHK(fz_flag_roundtrip(c, flags, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
         hipLaunchKernelGGL(k_prep_objects, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, ch.x, ch.xe, ch.xm,
                            n, B, BT, vmode, derive ? 1 : 0, c->d_ox.as<double>(), c->d_ov.as<double>(),
-                           c->d_obits.as<uint32_t>(), c->d_oslv.as<double>(), c->d_flags.as<int>(), c->d_ye2c.as<double>());
-    }
-    HIPCHK(hipGetLastError());
-    FZCHK(copy_out(c, &flags, c->d_flags.p, sizeof(int)));
+                           c->d_obits.as<uint32_t>(), c->d_oslv.as<double>(), d_flags, c->d_ye2c.as<double>());
+        return 0;
+    }));
     if (ch.staged) {
         FZCHK(copy_out(c, x + i0 * B, ch.x, raw)); FZCHK(copy_out(c, xe + i0 * B, ch.xe, raw)); FZCHK(copy_out(c, xm + i0 * B, ch.xm, raw));
     }
@@ -681,45 +704,18 @@ extern "C" int fz_clean(fz_ctx* c, double* x, double* xe, double* xm, int64_t N,
 // ---------------------------------------------------------------------------
 static int run_planes(fz_ctx* c, int mode, int var, int dp, int64_t n, double* lnl, double* chi2, int64_t* ndim,
                       double* scale, double* serr) {
-    switch (c->BT) {
-        case 4: return fz_planes_bt4(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 5: return fz_planes_bt5(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 6: return fz_planes_bt6(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 7: return fz_planes_bt7(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 8: return fz_planes_bt8(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 12: return fz_planes_bt12(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 16: return fz_planes_bt16(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        case 24: return fz_planes_bt24(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-        default: return fz_planes_bt32(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr);
-    }
+    const fz_bt_table* t = bt_lookup(c);
+    return t ? t->planes(c, mode, var, dp, n, lnl, chi2, ndim, scale, serr) : -5;
 }
 static int run_fitpredict(fz_ctx* c, int mode, int var, int dp, int64_t n, const fz_kde_opts* ko, double* lmap, double* levid,
                           double* pdfs) {
-    switch (c->BT) {
-        case 4: return fz_fitpredict_bt4(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 5: return fz_fitpredict_bt5(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 6: return fz_fitpredict_bt6(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 7: return fz_fitpredict_bt7(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 8: return fz_fitpredict_bt8(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 12: return fz_fitpredict_bt12(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 16: return fz_fitpredict_bt16(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        case 24: return fz_fitpredict_bt24(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-        default: return fz_fitpredict_bt32(c, mode, var, dp, n, ko, lmap, levid, pdfs);
-    }
+    const fz_bt_table* t = bt_lookup(c);
+    return t ? t->fitpredict(c, mode, var, dp, n, ko, lmap, levid, pdfs) : -5;
 }
 static int run_modec(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr = nullptr,
                      const int64_t* nnb = nullptr, int W = 0) {
-    switch (c->BT) {
-        case 4: return fz_modec_bt4(c, var, n, o, nbr, nnb, W);
-        case 5: return fz_modec_bt5(c, var, n, o, nbr, nnb, W);
-        case 6: return fz_modec_bt6(c, var, n, o, nbr, nnb, W);
-        case 7: return fz_modec_bt7(c, var, n, o, nbr, nnb, W);
-        case 8: return fz_modec_bt8(c, var, n, o, nbr, nnb, W);
-        case 12: return fz_modec_bt12(c, var, n, o, nbr, nnb, W);
-        case 16: return fz_modec_bt16(c, var, n, o, nbr, nnb, W);
-        case 24: return fz_modec_bt24(c, var, n, o, nbr, nnb, W);
-        default: return fz_modec_bt32(c, var, n, o, nbr, nnb, W);
-    }
+    const fz_bt_table* t = bt_lookup(c);
+    return t ? t->modec(c, var, n, o, nbr, nnb, W) : -5;
 }
 
 static int check_kde_opts(const fz_kde_opts* ko) {
@@ -736,24 +732,20 @@ static int run_cdf(fz_ctx* c, int64_t n, int L, int64_t M, const double* rows, c
     KdeView kv; const int rc = fz_kde_view(c, kv);
     c->M = savedM;
     if (rc) return rc;
-    FZCHK(c->d_kv.ensure(sizeof(KdeView)));
-    FZCHK(copy_in(c, c->d_kv.p, &kv, sizeof(KdeView)));
+    FZCHK(fz_upload_kv(c, kv));
     const size_t per_wave = (size_t)std::max(kv.acc_stride, 512) * 8;      // (the selection's 2 x 256-bucket histogram shares the row)
     int wpb = 4;
     while (wpb > 1 && per_wave * wpb > 64 * 1024) wpb >>= 1;
     const size_t lds = per_wave * wpb;
     HIPCHK(hipFuncSetAttribute((const void*)k_kde_cdf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    FZCHK(c->d_flags.ensure(64));
-    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-    {
+    int ef = 0;
+    FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_kde, &c->tm.n_kde);
         hipLaunchKernelGGL(k_kde_cdf, dim3((unsigned)((n + wpb - 1) / wpb)), dim3(wpb * 64), lds, c->stream,
                            c->d_kv.as<KdeView>(), kv.acc_stride, n, L, (int)M, rows, nbr, nnb, is_log, ko->cdf_thresh,
-                           ko->normalize, dp, dm, de, c->d_flags.as<int>());
-    }
-    HIPCHK(hipGetLastError());
-    int ef = 0;
-    FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+                           ko->normalize, dp, dm, de, d_flags);
+        return 0;
+    }));
     if (ef) return fail(-3, "neighbour table entry outside [0, Nmodel) or Nneighbors outside [0, K*k]");
     return 0;
 }
@@ -847,12 +839,11 @@ static int prior_chunk(fz_ctx* c, const PriorBind& pb, int64_t i0, int64_t n, in
         v.tab = pb.tab;
         if (pb.rows_dev) v.rows = pb.pr->rows + i0;
         else { FZCHK(c->d_prows.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_prows.p, pb.pr->rows + i0, (size_t)n * 8)); v.rows = c->d_prows.as<int64_t>(); }
-        FZCHK(c->d_flags.ensure(64));
-        HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-        hipLaunchKernelGGL(k_prior_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, n, pb.pr->P, c->d_flags.as<int>());
-        HIPCHK(hipGetLastError());
         int ef = 0;
-        FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+        FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
+            hipLaunchKernelGGL(k_prior_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, n, pb.pr->P, d_flags);
+            return 0;
+        }));
         if (ef) return fail(-3, "ln-prior row index outside [0, %lld)", (long long)pb.pr->P);
     }
     c->prior = v;
@@ -953,14 +944,13 @@ extern "C" int fz_fit_predict_prior(fz_ctx* c, double* x, double* xe, double* xm
         HIPCHK(hipMemcpyAsync(c->d_sx.p, x, raw, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_sxe.p, xe, raw, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_sxm.p, xm, raw, hipMemcpyHostToDevice, c->stream));
-        FZCHK(c->d_flags.ensure(64));
-        HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-        hipLaunchKernelGGL(k_prep_objects, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->d_sx.as<double>(), c->d_sxe.as<double>(),
-                           c->d_sxm.as<double>(), N, c->B, c->BT, 0, 0, (double*)nullptr, (double*)nullptr, (uint32_t*)nullptr, (double*)nullptr,
-                           c->d_flags.as<int>(), c->d_ye2c.as<double>());
-        HIPCHK(hipGetLastError());
         int fl = 0;
-        FZCHK(copy_out(c, &fl, c->d_flags.p, sizeof fl));
+        FZCHK(fz_flag_roundtrip(c, fl, [&](int* d_flags) {
+            hipLaunchKernelGGL(k_prep_objects, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->d_sx.as<double>(), c->d_sxe.as<double>(),
+                               c->d_sxm.as<double>(), N, c->B, c->BT, 0, 0, (double*)nullptr, (double*)nullptr, (uint32_t*)nullptr, (double*)nullptr,
+                               d_flags, c->d_ye2c.as<double>());
+            return 0;
+        }));
         if (fl & 2) return fail(-4, "data_mask must be binary (0/1)");
         if (fl & 8) {                                            // pdf.py:310-311 rewrote something: the caller's arrays see it
             FZCHK(copy_out(c, x, c->d_sx.p, raw)); FZCHK(copy_out(c, xe, c->d_sxe.p, raw)); FZCHK(copy_out(c, xm, c->d_sxm.p, raw));
@@ -972,6 +962,59 @@ extern "C" int fz_fit_predict_prior(fz_ctx* c, double* x, double* xe, double* xm
     }
     return fit_predict_impl(c, x, xe, xm, N, o, ko, pr, pdfs, lmap, levid);
 }
+// The kernel form of one prepared fit_predict chunk under the weight-threshold rule (modes A / Ai / B): the special forms in the order
+// they are tried.  Returns < 0: error; 0: the chunk is done; +1: no special form applies and the caller runs the chunk's own variant
+// through run_fitpredict.  (The band-count units answer the VAR_SEG / VAR_OBJMASK requests made here in the same three ways.)
+static int fitpredict_special_forms(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const fz_kde_opts* ko, double* d_lm,
+                                    double* d_le, double* d_pdf) {
+    // real-catalogue inputs (pdf.py:76-87 with models_mask / per-model models_err): masked MODELS in any mode, or objects with
+    // unobserved bands against per-model errors -- the one-pass kernel on the segmented model layout (fz_hist.h, SEG); +1: the
+    // form does not apply (too many mask patterns, a KDE form it does not take ...) and the chunk goes on as before
+    // ... with one dictionary kernel or many (per-model label errors: the layout is ordered by width class first).  Mask-free data
+    // with many widths keep k_fused's class-sorted stack (80 against 112 ms per 2.6e10 pairs: the per-class convolutions cost both
+    // kernels the same, and k_fused's weight-space loop has no group-by-group tiles at the class boundaries); FZ_HIST_SEG_MC=1
+    // sends them here too (tests); FZ_HIST_SEG_FORCE=1 sends mask-free single-width data through the segmented form (tests; the
+    // measure of what the form itself costs: +16 % / +25 % / +11 % on the same data in modes Ai / A / B).
+    const int smc = (int)fz_dbg_int("FZ_HIST_SEG_MC", -1);           // (unset, or neither 0 nor 1: masked sets only)
+    const bool many_widths = c->label_mode == 1 && !c->single_cls;
+    const bool masks = c->models_real_masked || var == VAR_MASKED;
+    const bool seg_mc = many_widths && c->mc_ok && smc != 0 && (masks || smc == 1);
+    if ((var == VAR_MASKED || var == VAR_FAST) && c->BT == c->B && !c->prior.tab &&
+        (many_widths ? seg_mc : (c->models_real_masked || (var == VAR_MASKED && mode == 0) || fz_dbg_set("FZ_HIST_SEG_FORCE")))) {
+        const int r0 = run_fitpredict(c, mode, VAR_SEG, dim_prior, n, ko, d_lm, d_le, d_pdf);
+        if (r0 <= 0) return r0;
+    }
+    // objects with unobserved bands, unmasked models, modes Ai / B: the one-pass kernel with per-object band counts takes the whole
+    // chunk (masked and fully observed objects alike); where it does not apply (+1) the chunk is split as before
+    if (var == VAR_MASKED && !c->models_real_masked && mode != 0 && !c->prior.tab) {
+        const int r0 = run_fitpredict(c, mode, VAR_OBJMASK, dim_prior, n, ko, d_lm, d_le, d_pdf);
+        if (r0 <= 0) return r0;
+    }
+    // A chunk with some unobserved bands would run the masked kernels for every object.
+    // When the models themselves are unmasked, the (usually large) share of objects with
+    // every band observed keeps the mask-free kernels: the chunk is split in two launches.
+    if (var == VAR_MASKED && !c->models_real_masked && (c->BT == c->B || c->BT > 8) && n >= 4096 && !fz_dbg_set("FZ_NO_SPLIT")) {
+        FZCHK(c->d_omap.ensure((size_t)n * 8 + 64));
+        int* fast = c->d_omap.as<int>(); int* slow = fast + n; int* counts = slow + n;
+        HIPCHK(hipMemsetAsync(counts, 0, 8, c->stream));
+        hipLaunchKernelGGL(k_partition_masked, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                           c->d_obits.as<uint32_t>(), n, (uint32_t)((1ull << c->B) - 1), fast, slow, counts);
+        HIPCHK(hipGetLastError());
+        int cnt[2] = {0, 0};
+        FZCHK(copy_out(c, cnt, counts, sizeof cnt));
+        if (cnt[0] >= 1024 && cnt[1] > 0) {
+            OmapGuard og{c};
+            c->omap = fast;
+            const int r1 = run_fitpredict(c, mode, pick_var(c, 0), dim_prior, cnt[0], ko, d_lm, d_le, d_pdf);
+            if (r1 < 0) return r1;
+            c->omap = slow;
+            const int r2 = (r1 == 0) ? run_fitpredict(c, mode, VAR_MASKED, dim_prior, cnt[1], ko, d_lm, d_le, d_pdf) : 2;
+            if (r2 < 0) return r2;
+            if (r1 == 0 && r2 == 0) return 0;                      // (else: the whole chunk again, below)
+        }
+    }
+    return 1;
+}
 static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
                             const fz_kde_opts* ko, const fz_prior* pr, double* pdfs, double* lmap, double* levid) {
     const int mode = eff_mode(c, like_mode(o));
@@ -982,14 +1025,14 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
     const bool cdf = !ko->use_wt_thresh;          // reference CDF rule: materialise the chunk's ln-like rows
     PriorBind pb; PriorGuard guard{c};
     FZCHK(prior_begin(c, pr, N, M, pb));
-    int64_t nc = std::min<int64_t>(N, fz_dbg("FZ_CHUNK") ? atoll(fz_dbg("FZ_CHUNK")) : (1 << 20));   // the fused kernel's workspace does not grow with the chunk
+    int64_t nc = std::min<int64_t>(N, fz_dbg_int("FZ_CHUNK", 1 << 20));   // the fused kernel's workspace does not grow with the chunk
     const int64_t per_obj = M * 8 * (mode == 3 ? 4 : (cdf ? 1 : 0)) + pb.chunk_bytes_per_obj;
     if (per_obj) nc = std::min<int64_t>(nc, std::max<int64_t>(1, c->ws_limit / per_obj));
     // Host PDFs are the bulk of the PCIe traffic of the drop-in call (5.6 GB at 1e6 objects, longer
     // than the kernel).  Pipeline: chunks of 2^17 objects, two device staging buffers, chunk k's rows
     // leave on a second stream while chunk k+1 is being computed; kernel timing is deferred so that
     // the host does not wait on a kernel before it has queued the previous chunk's copy.
-    const bool pipe = !pdf_dev && mode != 3 && !cdf && N >= (3 << 17) && !fz_dbg("FZ_NO_PIPELINE");
+    const bool pipe = !pdf_dev && mode != 3 && !cdf && N >= (3 << 17) && !fz_dbg_set("FZ_NO_PIPELINE");
     if (pipe) nc = std::min<int64_t>(nc, 1 << 17);               // (the last chunk's rows leave with nothing to hide behind: keep it small)
     struct PipeGuard {
         fz_ctx* c; bool on;
@@ -1055,56 +1098,9 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             if (c->prior.tab) FZCHK(prior_add(c, c->d_pl[0].as<double>(), n, M, nullptr, nullptr, nullptr, c->d_pl[0].as<double>()));
             FZCHK(run_cdf(c, n, (int)M, M, c->d_pl[0].as<double>(), nullptr, nullptr, 1, ko, d_pdf, d_lm, d_le));
         } else {
-            // A chunk with some unobserved bands would run the masked kernels for every object.
-            // When the models themselves are unmasked, the (usually large) share of objects with
-            // every band observed keeps the mask-free kernels: the chunk is split in two launches.
-            bool done = false;
-            // real-catalogue inputs (pdf.py:76-87 with models_mask / per-model models_err): masked MODELS in any mode, or objects with
-            // unobserved bands against per-model errors -- the one-pass kernel on the segmented model layout (fz_hist.h, SEG); +1: the
-            // form does not apply (too many mask patterns, a KDE form it does not take ...) and the chunk goes on as before
-            // ... with one dictionary kernel or many (per-model label errors: the layout is ordered by width class first).  Mask-free data
-            // with many widths keep k_fused's class-sorted stack (80 against 112 ms per 2.6e10 pairs: the per-class convolutions cost both
-            // kernels the same, and k_fused's weight-space loop has no group-by-group tiles at the class boundaries); FZ_HIST_SEG_MC=1
-            // sends them here too (tests); FZ_HIST_SEG_FORCE=1 sends mask-free single-width data through the segmented form (tests; the
-            // measure of what the form itself costs: +16 % / +25 % / +11 % on the same data in modes Ai / A / B).
-            const char* smc = fz_dbg("FZ_HIST_SEG_MC");
-            const bool many_widths = c->label_mode == 1 && !c->single_cls;
-            const bool masks = c->models_real_masked || var == VAR_MASKED;
-            const bool seg_mc = many_widths && c->mc_ok && !(smc && atoi(smc) == 0) && (masks || (smc && atoi(smc) == 1));
-            if ((var == VAR_MASKED || var == VAR_FAST) && c->BT == c->B && !c->prior.tab &&
-                (many_widths ? seg_mc : (c->models_real_masked || (var == VAR_MASKED && mode == 0) || fz_dbg("FZ_HIST_SEG_FORCE")))) {
-                const int r0 = run_fitpredict(c, mode, VAR_SEG, o->dim_prior, n, ko, d_lm, d_le, d_pdf);
-                if (r0 < 0) return r0;
-                done = (r0 == 0);
-            }
-            // objects with unobserved bands, unmasked models, modes Ai / B: the one-pass kernel with per-object band counts takes the whole
-            // chunk (masked and fully observed objects alike); where it does not apply (+1) the chunk is split as before
-            if (!done && var == VAR_MASKED && !c->models_real_masked && mode != 0 && !c->prior.tab) {
-                const int r0 = run_fitpredict(c, mode, VAR_OBJMASK, o->dim_prior, n, ko, d_lm, d_le, d_pdf);
-                if (r0 < 0) return r0;
-                done = (r0 == 0);
-            }
-            if (!done && var == VAR_MASKED && !c->models_real_masked && (c->BT == c->B || c->BT > 8) && n >= 4096 && !fz_dbg("FZ_NO_SPLIT")) {
-                FZCHK(c->d_omap.ensure((size_t)n * 8 + 64));
-                int* fast = c->d_omap.as<int>(); int* slow = fast + n; int* counts = slow + n;
-                HIPCHK(hipMemsetAsync(counts, 0, 8, c->stream));
-                hipLaunchKernelGGL(k_partition_masked, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                                   c->d_obits.as<uint32_t>(), n, (uint32_t)((1ull << c->B) - 1), fast, slow, counts);
-                HIPCHK(hipGetLastError());
-                int cnt[2] = {0, 0};
-                FZCHK(copy_out(c, cnt, counts, sizeof cnt));
-                if (cnt[0] >= 1024 && cnt[1] > 0) {
-                    OmapGuard og{c};
-                    c->omap = fast;
-                    const int r1 = run_fitpredict(c, mode, pick_var(c, 0), o->dim_prior, cnt[0], ko, d_lm, d_le, d_pdf);
-                    if (r1 < 0) return r1;
-                    c->omap = slow;
-                    const int r2 = (r1 == 0) ? run_fitpredict(c, mode, VAR_MASKED, o->dim_prior, cnt[1], ko, d_lm, d_le, d_pdf) : 2;
-                    if (r2 < 0) return r2;
-                    done = (r1 == 0 && r2 == 0);
-                }
-            }
-            if (!done) FZCHK(run_fitpredict(c, mode, var, o->dim_prior, n, ko, d_lm, d_le, d_pdf));
+            const int r = fitpredict_special_forms(c, mode, var, o->dim_prior, n, ko, d_lm, d_le, d_pdf);
+            if (r < 0) return r;
+            if (r > 0) FZCHK(run_fitpredict(c, mode, var, o->dim_prior, n, ko, d_lm, d_le, d_pdf));
         }
         if (pipe) {
             HIPCHK(hipEventRecord(c->ev_done[bsel], c->stream));          // chunk k is queued ...

@@ -34,6 +34,7 @@ inline int fail(int code, const char* fmt, ...) {
 // The model arrays are padded to whole LDS tiles of every kernel that stages them: k_fused up to 1024 models, k_hist 256 / 128 / 64
 // or 384 (FZ_HIST_TILE384): the least common multiple
 #define FZ_MP_ALIGN 3072
+inline int64_t fz_padded_models(int64_t M) { return (M + FZ_MP_ALIGN - 1) / FZ_MP_ALIGN * FZ_MP_ALIGN; }
 
 // ---- grow-only cached device allocation ----------------------------------------
 struct DevBuf {
@@ -52,8 +53,10 @@ struct DevBuf {
 };
 
 // Test / tuning switches ("FZ_..." names): set by ONE call, fz_debug_opts (include/frankenz_hip.h) -- the library does not read the
-// environment.  nullptr when the switch is not set (the meaning getenv had for the code that consults it).
-const char* fz_dbg(const char* name);
+// environment.  Every answer is a value formed under the lock fz_debug_opts takes (never a pointer into the table it replaces).
+bool fz_dbg_set(const char* name);                          // the switch is present, whatever its value (what "the variable is set" meant when the environment was read)
+long long fz_dbg_int(const char* name, long long unset);    // atoll of its value (text that is no number reads 0); `unset` when not present
+std::string fz_dbg_str(const char* name);                   // a copy of its value; empty when not present
 
 struct fz_ctx {
     int device = 0;
@@ -104,6 +107,9 @@ struct fz_ctx {
     // records sorted by (dictionary class, mask pattern), segments padded to whole 64-model groups.  Built on first use from the host
     // copies below (fz_segments); seg_state: 0 not built, 1 built, -1 this model / label set does not take the form
     std::vector<uint32_t> h_mbits; std::vector<int32_t> h_pos, h_cls;
+    // dictionary labels: rank of every dictionary class among the classes present, in dictionary order (-1: absent), and how many are
+    // present -- the class order of the class-sorted stack and of the segments (fz_labels_upload_dict)
+    std::vector<int32_t> h_rank; int32_t n_rank = 0;
     int seg_state = 0; int64_t seg_Ms = 0; int32_t seg_n = 0, seg_nrank = 0; bool seg_rec0_valid = false, seg_rec1_valid = false;
     DevBuf d_seg_tag, d_seg_perm, d_seg_mask, d_seg_rank, d_seg_start, d_seg_rec0, d_seg_rec1;
     // per-chunk object buffers
@@ -237,23 +243,22 @@ inline int pick_var(fz_ctx* c, int obj_flags) {
 int fz_segments(fz_ctx* c, bool rec0);
 
 // ---- per-band-count launchers (fz_inst.hip, one translation unit per BT) ------
-#define FZ_DECL_BT(N)                                                                                     \
-    int fz_planes_bt##N(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, double* lnl, double* chi2, \
-                        int64_t* ndim, double* scale, double* serr);                                      \
-    int fz_fitpredict_bt##N(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const fz_kde_opts* ko, \
-                            double* lmap, double* levid, double* pdfs);                                   \
-    int fz_modec_bt##N(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr,           \
-                       const int64_t* nnb, int W);                             \
-    int fz_knnsubset_bt##N(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const int64_t* idx, int W, \
-                           const fz_kde_opts* ko, const fz::KnnOut* out, int* errflag);                   \
-    int fz_knnquery_bt##N(fz_ctx* c, const double* q, int64_t n, int k, double bound2, int64_t* idx, int pnorm);
-FZ_DECL_BT(4)
-FZ_DECL_BT(5)
-FZ_DECL_BT(6)
-FZ_DECL_BT(7)
-FZ_DECL_BT(8)
-FZ_DECL_BT(12)
-FZ_DECL_BT(16)
-FZ_DECL_BT(24)
-FZ_DECL_BT(32)
-#undef FZ_DECL_BT
+// The band counts the library is compiled for, ascending.  This is the only list inside the library: the padded band count of a model
+// set (pick_bt), the table lookup (bt_lookup; both frankenz_hip.hip) and the stub tables of a development build (tools/dev_stubs.hip) expand it.
+#define FZ_BT_LIST(X) X(4) X(5) X(6) X(7) X(8) X(12) X(16) X(24) X(32)
+// what one unit exports: the constant table of its five entry points
+struct fz_bt_table {
+    int BT;
+    int (*planes)(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, double* lnl, double* chi2, int64_t* ndim, double* scale,
+                  double* serr);
+    int (*fitpredict)(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const fz_kde_opts* ko, double* lmap, double* levid,
+                      double* pdfs);
+    int (*modec)(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr, const int64_t* nnb, int W);
+    int (*knnsubset)(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const int64_t* idx, int W, const fz_kde_opts* ko,
+                     const fz::KnnOut* out, int* errflag);
+    int (*knnquery)(fz_ctx* c, const double* q, int64_t n, int k, double bound2, int64_t* idx, int pnorm);
+};
+// (handed out by a function: a const object at namespace scope would be emitted into the device code object as well)
+#define FZ_BT_DECL(N) const fz_bt_table* fz_bt_unit_##N();
+FZ_BT_LIST(FZ_BT_DECL)
+#undef FZ_BT_DECL

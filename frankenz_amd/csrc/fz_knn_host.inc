@@ -39,7 +39,7 @@ extern "C" int fz_knn_upload_trees(fz_ctx* c, const float* feats, int32_t K, int
         // (a node over tiles [a, b) splits at a + (b - a) / 2): tab[set][tile][2] = {split feature, split value (float bits)} of the
         // internal node whose right half starts at that tile -- what a query needs to find its leaf (knn_kd_leaf).
         // Needs the free slot 7 of the B operand for the original index (F <= 5) and indices that a float holds exactly.
-        const bool sorted = F <= 5 && M < (1 << 24) && !fz_dbg("FZ_KNN_NOSORT");
+        const bool sorted = F <= 5 && M < (1 << 24) && !fz_dbg_set("FZ_KNN_NOSORT");
         if (sorted) {
             std::vector<float> h((size_t)K * M * F);
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -120,7 +120,7 @@ static void kmstats_dump(fz_ctx* c, const char* what) {
 #define KMSTATS_DUMP(c, w) do { } while (0)
 #endif
 static bool knn_on_matrix_pipe(const fz_ctx* c, int pnorm) {
-    return pnorm == 2 && c->knn_mfma && !fz_dbg("FZ_KNN_FP64") && !fz_dbg("FZ_KNN_NOMFMA");
+    return pnorm == 2 && c->knn_mfma && !fz_dbg_set("FZ_KNN_FP64") && !fz_dbg_set("FZ_KNN_NOMFMA");
 }
 // k beyond one wave's width (64) is served by the matrix-pipe search only (lists in LDS, 64-entry segments)
 static int check_knn_k(const fz_ctx* c, int k, int pnorm, const char* who) {
@@ -132,7 +132,7 @@ static int check_knn_k(const fz_ctx* c, int k, int pnorm, const char* who) {
 static int run_knnquery(fz_ctx* c, const double* q, int64_t n, int k, double b2, int64_t* idx, int pnorm) {
     if (knn_on_matrix_pipe(c, pnorm)) {
         // register lists (row-parallel admissions) for k <= 32, the reference's default is 20; FZ_KNN_SERIAL=1: the wave-serial LDS lists
-        const int kpl = fz_dbg("FZ_KNN_SERIAL") ? 0 : (k <= 20 ? 5 : (k <= 32 ? 8 : 0));
+        const int kpl = fz_dbg_set("FZ_KNN_SERIAL") ? 0 : (k <= 20 ? 5 : (k <= 32 ? 8 : 0));
         const int kpad = std::max((k + 3) & ~3, 4 * kpl);
         // one wave per block with its own 64-model tiles: no barrier skew between waves whose admission paths differ in
         // length, and every wave scans from its own queries' place (shared 128-model tiles for four waves measured 79.9 ms
@@ -158,7 +158,7 @@ static int run_knnquery(fz_ctx* c, const double* q, int64_t n, int k, double b2,
                                c->d_kqperm.as<int>(), c->d_ktab.as<int>(), kdn);
             qperm = c->d_kqperm.as<int>(); ktab = c->d_ktab.as<int>();
         }
-        const bool skip = c->knn_sorted && !fz_dbg("FZ_KNN_NOBOX");      // (storage order: boxes exclude nothing)
+        const bool skip = c->knn_sorted && !fz_dbg_set("FZ_KNN_NOBOX");      // (storage order: boxes exclude nothing)
         const float* gbx = skip ? c->d_kgbox.as<float>() : nullptr;
         const float* tbx = skip ? c->d_ktbox.as<float>() : nullptr;
         Timer t(c, &c->tm.ms_knn, &c->tm.n_knn);
@@ -170,31 +170,13 @@ static int run_knnquery(fz_ctx* c, const double* q, int64_t n, int k, double b2,
         HIPCHK(hipGetLastError());
         return 0;
     }
-    switch (c->BT) {
-        case 4: return fz_knnquery_bt4(c, q, n, k, b2, idx, pnorm);
-        case 5: return fz_knnquery_bt5(c, q, n, k, b2, idx, pnorm);
-        case 6: return fz_knnquery_bt6(c, q, n, k, b2, idx, pnorm);
-        case 7: return fz_knnquery_bt7(c, q, n, k, b2, idx, pnorm);
-        case 8: return fz_knnquery_bt8(c, q, n, k, b2, idx, pnorm);
-        case 12: return fz_knnquery_bt12(c, q, n, k, b2, idx, pnorm);
-        case 16: return fz_knnquery_bt16(c, q, n, k, b2, idx, pnorm);
-        case 24: return fz_knnquery_bt24(c, q, n, k, b2, idx, pnorm);
-        default: return fz_knnquery_bt32(c, q, n, k, b2, idx, pnorm);
-    }
+    const fz_bt_table* t = bt_lookup(c);
+    return t ? t->knnquery(c, q, n, k, b2, idx, pnorm) : -5;
 }
 static int run_knnsubset(fz_ctx* c, int mode, int var, int dp, int64_t n, const int64_t* idx, int W, const fz_kde_opts* ko,
                          const KnnOut* out, int* ef) {
-    switch (c->BT) {
-        case 4: return fz_knnsubset_bt4(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 5: return fz_knnsubset_bt5(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 6: return fz_knnsubset_bt6(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 7: return fz_knnsubset_bt7(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 8: return fz_knnsubset_bt8(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 12: return fz_knnsubset_bt12(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 16: return fz_knnsubset_bt16(c, mode, var, dp, n, idx, W, ko, out, ef);
-        case 24: return fz_knnsubset_bt24(c, mode, var, dp, n, idx, W, ko, out, ef);
-        default: return fz_knnsubset_bt32(c, mode, var, dp, n, idx, W, ko, out, ef);
-    }
+    const fz_bt_table* t = bt_lookup(c);
+    return t ? t->knnsubset(c, mode, var, dp, n, idx, W, ko, out, ef) : -5;
 }
 
 // launch k_knn_predict on device-resident chunk buffers
@@ -205,23 +187,19 @@ static int knn_predict_chunk(fz_ctx* c, int64_t n, int64_t M, const double* dl, 
     KdeView kv; const int rc = fz_kde_view(c, kv);
     c->M = savedM;
     if (rc) return rc;
-    FZCHK(c->d_kv.ensure(sizeof(KdeView)));
-    FZCHK(copy_in(c, c->d_kv.p, &kv, sizeof(KdeView)));
+    FZCHK(fz_upload_kv(c, kv));
     int wpb = 4;
     while (wpb > 1 && (size_t)kv.acc_stride * 8 * wpb > 64 * 1024) wpb >>= 1;
     const size_t lds = (size_t)kv.acc_stride * 8 * wpb;
     HIPCHK(hipFuncSetAttribute((const void*)k_knn_predict, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    FZCHK(c->d_flags.ensure(64));
-    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
-    {
+    int ef = 0;
+    FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_knn, &c->tm.n_knn);
         hipLaunchKernelGGL(k_knn_predict, dim3((unsigned)((n + wpb - 1) / wpb)), dim3(wpb * 64), lds, c->stream,
                            c->d_kv.as<KdeView>(), kv.acc_stride, n, (int)M, dl, dn, dc, W, ko->wt_thresh, ko->normalize,
-                           dp, dm, de, c->d_flags.as<int>());
-    }
-    HIPCHK(hipGetLastError());
-    int ef = 0;
-    FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+                           dp, dm, de, d_flags);
+        return 0;
+    }));
     if (ef) return fail(-3, "neighbour table entry outside [0, Nmodel) or Nneighbors outside [0, K*k]");
     return 0;
 }
@@ -306,12 +284,9 @@ extern "C" int fz_knn_fit_predict_prior(fz_ctx* c, double* x, double* xe, double
         KnnOut ko_; ko_.neighbors = (int64_t*)outs[0].dev; ko_.nnbr = (int64_t*)outs[1].dev; ko_.lnlike = (double*)outs[2].dev;
         ko_.chi2 = (double*)outs[3].dev; ko_.ndim = (int64_t*)outs[4].dev; ko_.scale = (double*)outs[5].dev;
         ko_.serr = (double*)outs[6].dev; ko_.pdfs = (double*)outs[7].dev; ko_.lmap = (double*)outs[8].dev; ko_.levid = (double*)outs[9].dev;
-        FZCHK(c->d_flags.ensure(64));
-        HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
         int ef = 0;
         if (!rows_route) {
-            FZCHK(run_knnsubset(c, mode, var, o->dim_prior, n, di, (int)W, ko, &ko_, c->d_flags.as<int>()));
-            FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+            FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) { return run_knnsubset(c, mode, var, o->dim_prior, n, di, (int)W, ko, &ko_, d_flags); }));
         } else {
             int64_t* nb = ko_.neighbors; int64_t* nn = ko_.nnbr;
             if (!nb) { FZCHK(c->d_nbr.ensure((size_t)n * W * 8)); nb = c->d_nbr.as<int64_t>(); }
@@ -324,13 +299,12 @@ extern "C" int fz_knn_fit_predict_prior(fz_ctx* c, double* x, double* xe, double
                 while (dw > 1 && (size_t)dw * 5 * fz_knn_wcap((int)W) * 4 > 64 * 1024) dw >>= 1;
                 const size_t dl = (size_t)dw * 5 * fz_knn_wcap((int)W) * 4;
                 HIPCHK(hipFuncSetAttribute((const void*)k_knn_dedup, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl));
-                {
+                FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
                     Timer t(c, &c->tm.ms_knn, &c->tm.n_knn);
                     hipLaunchKernelGGL(k_knn_dedup, dim3((unsigned)((n + dw - 1) / dw)), dim3(dw * 64), dl, c->stream, n, (int)c->M, di, (int)W, nb, nn,
-                                       c->d_flags.as<int>());
-                }
-                HIPCHK(hipGetLastError());
-                FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+                                       d_flags);
+                    return 0;
+                }));
                 if (!ef) {
                     FZCHK(run_modec(c, var, n, o, nb, nn, (int)W));
                     if (!lpl) lpl = c->d_mc[1].as<double>();                     // in place on the state plane
@@ -341,8 +315,7 @@ extern "C" int fz_knn_fit_predict_prior(fz_ctx* c, double* x, double* xe, double
                 k2.neighbors = nb; k2.nnbr = nn; k2.pdfs = nullptr;
                 if (!lpl) { FZCHK(c->d_mc[1].ensure((size_t)n * W * 8)); lpl = c->d_mc[1].as<double>(); }
                 k2.lnlike = lpl;
-                FZCHK(run_knnsubset(c, mode, var, o->dim_prior, n, di, (int)W, ko, &k2, c->d_flags.as<int>()));
-                FZCHK(copy_out(c, &ef, c->d_flags.p, sizeof ef));
+                FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) { return run_knnsubset(c, mode, var, o->dim_prior, n, di, (int)W, ko, &k2, d_flags); }));
             }
             if (!ef) {
                 const double* lw = lpl;

@@ -6,6 +6,44 @@
 #include "fz_hist.h"
 #include "fz_plane.h"
 
+// ---- launch helpers ------------------------------------------------------------
+// LDS of one compute unit of gfx950: the most a block can be given (static + dynamic)
+constexpr size_t FZ_LDS_BYTES = 160 * 1024;
+
+// The KDE table view of a launch goes to c->d_kv (slot 0; `second`, when given, to slot 1).  Waits for the copy: the views are stack
+// objects of the caller.
+inline int fz_upload_kv(fz_ctx* c, const fz::KdeView& kv, const fz::KdeView* second = nullptr) {
+    FZCHK(c->d_kv.ensure((second ? 2 : 1) * sizeof(fz::KdeView)));
+    HIPCHK(hipMemcpyAsync(c->d_kv.p, &kv, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
+    if (second) HIPCHK(hipMemcpyAsync(c->d_kv.as<fz::KdeView>() + 1, second, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Grid of a kernel whose blocks stay resident: allows `lds` bytes of dynamic LDS, asks how many blocks of `threads` one CU holds
+// (*bpc_out, at least 1) and answers min(need, that * CUs).
+template <class K>
+int fz_resident_blocks(fz_ctx* c, K kern, int threads, size_t lds, int64_t need, int64_t& blocks, int* bpc_out = nullptr) {
+    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int bpc = 1;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)kern, threads, lds));
+    bpc = std::max(1, bpc);
+    if (bpc_out) *bpc_out = bpc;
+    blocks = std::min<int64_t>(need, (int64_t)bpc * c->cu_count);
+    return 0;
+}
+
+// One launch that reports through the device flag word: c->d_flags is cleared, `launch(int* d_flags)` queues the kernel (non-zero: its
+// error), the word is read back into `flags` (waits for the stream).  What a set bit means, and the error text, is the caller's.
+template <class L>
+int fz_flag_roundtrip(fz_ctx* c, int& flags, L&& launch) {
+    FZCHK(c->d_flags.ensure(64));
+    HIPCHK(hipMemsetAsync(c->d_flags.p, 0, 64, c->stream));
+    FZCHK(launch(c->d_flags.as<int>()));
+    HIPCHK(hipGetLastError());
+    return copy_out(c, &flags, c->d_flags.p, sizeof(int));
+}
+
 inline int fz_kde_view(fz_ctx* c, fz::KdeView& kv) {
     using namespace fz;
     if (c->label_mode == 0) return fail(-1, "labels have not been uploaded");
@@ -24,12 +62,12 @@ inline int fz_kde_view(fz_ctx* c, fz::KdeView& kv) {
     } else {
         kv.ly = c->d_ly.as<double>(); kv.lstd = c->d_lstd.as<double>(); kv.lo = c->d_lo.as<int32_t>(); kv.hi = c->d_hi.as<int32_t>();
         kv.grid = c->d_grid.as<double>();
-        kv.gstep = fz_dbg("FZ_GRID_RECUR") && atoi(fz_dbg("FZ_GRID_RECUR")) == 0 ? 0.0 : c->grid_step;
+        kv.gstep = fz_dbg_int("FZ_GRID_RECUR", 1) == 0 ? 0.0 : c->grid_step;
         kv.lrec = c->d_lrec.as<double>();
         kv.kmode = KDE_GRID; kv.acc_stride = (int)c->G;
     }
-    kv.lane_window = fz_dbg("FZ_LANE_WINDOW") ? atoi(fz_dbg("FZ_LANE_WINDOW")) : FZ_LANE_WINDOW;
-    if ((size_t)kv.acc_stride * 8 > 160 * 1024)
+    kv.lane_window = (int)fz_dbg_int("FZ_LANE_WINDOW", FZ_LANE_WINDOW);
+    if ((size_t)kv.acc_stride * 8 > FZ_LDS_BYTES)
         return fail(-5, "PDF grid of %lld points needs %zu B of LDS per object (> 160 KiB)", (long long)kv.G,
                     (size_t)kv.acc_stride * 8);
     return 0;
@@ -66,7 +104,7 @@ int fz_launch_kde(fz_ctx* c, const SRC& src, int64_t n, int64_t M, int linear, c
     fz::KdeView kv;
     FZCHK(fz_kde_view(c, kv));
     // objects per wave / waves per block from the LDS each object's accumulator needs
-    const size_t per_obj = (size_t)kv.acc_stride * 8, budget = 160 * 1024;
+    const size_t per_obj = (size_t)kv.acc_stride * 8, budget = FZ_LDS_BYTES;
     if (per_obj * 8 <= 53 * 1024) return fz_launch_kde_tw<SRC, 2>(c, src, kv, 4, n, M, linear, lmap, levid, ko, pdfs);
     if (per_obj * 4 <= budget) return fz_launch_kde_tw<SRC, 1>(c, src, kv, 4, n, M, linear, lmap, levid, ko, pdfs);
     if (per_obj * 2 <= budget) return fz_launch_kde_tw<SRC, 1>(c, src, kv, 2, n, M, linear, lmap, levid, ko, pdfs);
@@ -83,14 +121,10 @@ int fz_launch_plane_rows_g(fz_ctx* c, const double* plane, const fz::KdeView& kv
     // columns | parked ties | the kernel taps as matrix operands
     const size_t lds = ((size_t)FZ_HEXP_K + 4 * (size_t)kv.acc_stride + 6 * NW + 2) * 8 + (2 * NW + 2) * 4 + NT * E2 * 4 + NT * 12 +
                        (size_t)fz::plane_conv_ksteps(2 * kv.w0) * 64 * 8;
-    if (lds > 160 * 1024) return 1;
-    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int bpc = 1;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)kern, NW * 64, lds));
-    const int64_t blocks = std::min<int64_t>(n, (int64_t)std::max(1, bpc) * c->cu_count);
-    FZCHK(c->d_kv.ensure(sizeof(fz::KdeView)));
-    HIPCHK(hipMemcpyAsync(c->d_kv.p, &kv, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));          // kv is a stack object
+    if (lds > FZ_LDS_BYTES) return 1;
+    int64_t blocks = 0;
+    FZCHK(fz_resident_blocks(c, kern, NW * 64, lds, n, blocks));
+    FZCHK(fz_upload_kv(c, kv));
     Timer t(c, &c->tm.ms_fused, &c->tm.n_fused);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, plane, M, c->d_kv.as<fz::KdeView>(), kv.acc_stride, n,
                        (int)M, ko->wt_thresh, ko->normalize, lmap, levid, pdfs);
@@ -142,25 +176,21 @@ inline int fz_launch_plane_predict(fz_ctx* c, const double* plane, int64_t n, in
     const bool vec2 = (M % 2 == 0) && (((uintptr_t)plane & 15) == 0);
     const bool ho = kv.kmode == KDE_HIST;              // single-kernel label sets: the instantiation without the window code
     // the weights below wt_thresh of the best in fp32 unless the caller asked for the all-fp64 logsumexp (or thresholds nothing)
-    const bool x32 = !ko->exact_evidence && !c->exact_evidence && !fz_dbg("FZ_EXACT_EVIDENCE") && ko->wt_thresh > 0.0;
+    const bool x32 = !ko->exact_evidence && !c->exact_evidence && !fz_dbg_set("FZ_EXACT_EVIDENCE") && ko->wt_thresh > 0.0;
     auto kern = x32 ? (vec2 ? (ho ? k_plane_fused<NW, 2, true, true> : k_plane_fused<NW, 2, false, true>)
                             : (ho ? k_plane_fused<NW, 1, true, true> : k_plane_fused<NW, 1, false, true>))
                     : (vec2 ? (ho ? k_plane_fused<NW, 2, true, false> : k_plane_fused<NW, 2, false, false>)
                             : (ho ? k_plane_fused<NW, 1, true, false> : k_plane_fused<NW, 1, false, false>));
     // rows that fit one block's registers: exact maximum first, then fp64 weights straight into the LDS histogram (fz_plane.h)
-    if (!linear && !c->force_twopass && !fz_dbg("FZ_PLANE_TWOPASS") && vec2 && ho && kv.normtab && ko->wt_thresh >= 0.0 &&
-        (!fz_dbg("FZ_PLANE_ROWS") || atoi(fz_dbg("FZ_PLANE_ROWS")) != 0)) {
+    if (!linear && !c->force_twopass && !fz_dbg_set("FZ_PLANE_TWOPASS") && vec2 && ho && kv.normtab && ko->wt_thresh >= 0.0 &&
+        fz_dbg_int("FZ_PLANE_ROWS", 1) != 0) {
         const int r = fz_launch_plane_rows(c, plane, kv, n, M, ko, lmap, levid, pdfs);
         if (r <= 0) return r;
     }
     int64_t blocks = 0;
-    if (!linear && !c->force_twopass && !fz_dbg("FZ_PLANE_TWOPASS") && lds <= 160 * 1024 && M < ((int64_t)1 << 31)) {
-        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int bpc = 1;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)kern, NW * 64, lds));
-        const int64_t need = (n + NW - 1) / NW;
+    if (!linear && !c->force_twopass && !fz_dbg_set("FZ_PLANE_TWOPASS") && lds <= FZ_LDS_BYTES && M < ((int64_t)1 << 31)) {
+        FZCHK(fz_resident_blocks(c, kern, NW * 64, lds, (n + NW - 1) / NW, blocks));
         const int64_t fit = (int64_t)(c->ws_limit / ((size_t)M * sizeof(Cand) * NW));
-        blocks = std::min<int64_t>(need, (int64_t)std::max(1, bpc) * c->cu_count);
         if (fit < blocks) blocks = (fit >= c->cu_count) ? (fit / c->cu_count) * c->cu_count : 0;   // whole CUs or not at all
         if (blocks > 0 && c->d_cand.ensure((size_t)blocks * NW * M * sizeof(Cand)) != 0) blocks = 0;
     }
@@ -169,9 +199,7 @@ inline int fz_launch_plane_predict(fz_ctx* c, const double* plane, int64_t n, in
         FZCHK(fz_launch_stats(c, ps, n, M, linear, lmap, levid));
         return fz_launch_kde(c, ps, n, M, linear, lmap, levid, ko, pdfs);
     }
-    FZCHK(c->d_kv.ensure(sizeof(KdeView)));
-    HIPCHK(hipMemcpyAsync(c->d_kv.p, &kv, sizeof(KdeView), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    FZCHK(fz_upload_kv(c, kv));
     Timer t(c, &c->tm.ms_fused, &c->tm.n_fused);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, plane, M, c->d_kv.as<KdeView>(),
                        kv.acc_stride, n, (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<Cand>(), M, lmap, levid, pdfs);
@@ -213,7 +241,7 @@ int fz_launch_fused_wm(fz_ctx* c, const SRC& src_in, const fz::KdeView& kv_in, i
     // present (fz_kernels.h, pdf_stage_mc); FZ_NO_MC=1 keeps the per-model window adds
     bool mc = false;
     if constexpr (WM && (NW == 12 || NW == 4)) {      // (2,16) spills inside the model loop with this PDF stage: the dispatcher sends it to (2,12)
-        if (kv.kmode == fz::KDE_DICT && c->mc_ok && !fz_dbg("FZ_NO_MC")) {
+        if (kv.kmode == fz::KDE_DICT && c->mc_ok && !fz_dbg_set("FZ_NO_MC")) {
             FZCHK(fz_mc_records(c, SRC::LMODE == 0));
             src.mv.rec0 = c->d_rec0p.as<double>(); src.mv.rec1 = c->d_rec1p.as<double>();
             kv.mc_tag = c->d_mc_tag.as<int32_t>(); kv.mc_width = c->d_mc_width.as<int32_t>(); kv.mc_off = c->d_mc_off.as<int64_t>();
@@ -231,18 +259,16 @@ int fz_launch_fused_wm(fz_ctx* c, const SRC& src_in, const fz::KdeView& kv_in, i
     {
         hipFuncAttributes fa;
         HIPCHK(hipFuncGetAttributes(&fa, (const void*)kern));
-        if (fa.sharedSizeBytes + lds > 160 * 1024) return 1;
+        if (fa.sharedSizeBytes + lds > FZ_LDS_BYTES) return 1;
     }
     const int64_t groups = (n + TW - 1) / TW;
     const size_t per_wave = (size_t)TW * M * sizeof(fz::Cand);
-    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks_per_cu = 1;           // resident blocks per CU for this kernel's registers and LDS
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, (const void*)kern, NW * 64, lds));
-    blocks_per_cu = std::max(1, blocks_per_cu);
     // whole multiples of the CU count (an uneven tail of blocks would idle most CUs)
     const int64_t need = (groups + NW - 1) / NW;
     const int64_t fit = (int64_t)(c->ws_limit / (per_wave * NW));
-    int64_t blocks = need;
+    int blocks_per_cu = 1;           // resident blocks per CU for this kernel's registers and LDS
+    int64_t blocks = need;           // (what the helper answers while need <= CUs)
+    FZCHK(fz_resident_blocks(c, kern, NW * 64, lds, need, blocks, &blocks_per_cu));
     if (need > c->cu_count) {
         const int64_t k = std::min<int64_t>(blocks_per_cu, fit / c->cu_count);
         if (k >= 1) blocks = std::min<int64_t>(need, k * c->cu_count);
@@ -250,16 +276,13 @@ int fz_launch_fused_wm(fz_ctx* c, const SRC& src_in, const fz::KdeView& kv_in, i
         else return 1;                                             // cannot fill even half the chip
     } else if (fit < need) return 1;
     if (c->d_cand.ensure((size_t)blocks * NW * per_wave) != 0) return 1;      // no room for the lists: two-pass route
-    // slot 0: the view of the main launch; slot 1: the caller's view (the sweep below always runs the general kernels)
-    FZCHK(c->d_kv.ensure(2 * sizeof(fz::KdeView)));
-    HIPCHK(hipMemcpyAsync(c->d_kv.p, &kv, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_kv.as<fz::KdeView>() + 1, &kv_in, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
     // objects the weight-space body hands back (no candidate / no fp32 weight at all): counter + list
     if (WM) {
         FZCHK(c->d_redo.ensure(((size_t)n + 1) * sizeof(int)));
         HIPCHK(hipMemsetAsync(c->d_redo.p, 0, sizeof(int), c->stream));
     }
-    HIPCHK(hipStreamSynchronize(c->stream));          // kv is a stack object
+    // slot 0: the view of the main launch; slot 1: the caller's view (the sweep below always runs the general kernels)
+    FZCHK(fz_upload_kv(c, kv, &kv_in));
     {
         Timer t(c, &c->tm.ms_fused, &c->tm.n_fused);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, src, c->d_kv.as<fz::KdeView>(),
@@ -275,10 +298,10 @@ int fz_launch_fused_wm(fz_ctx* c, const SRC& src_in, const fz::KdeView& kv_in, i
             {
                 hipFuncAttributes fa;
                 HIPCHK(hipFuncGetAttributes(&fa, (const void*)sweep));
-                if (fa.sharedSizeBytes + lds2 > 160 * 1024) lds2 = (size_t)1 << 30;      // cannot run: the objects keep their (flagged) rows
+                if (fa.sharedSizeBytes + lds2 > FZ_LDS_BYTES) lds2 = (size_t)1 << 30;      // cannot run: the objects keep their (flagged) rows
             }
             const int64_t sblocks = std::min<int64_t>(std::min<int64_t>(c->cu_count, (n + SW - 1) / SW), (int64_t)((size_t)blocks * NW * per_wave / ((size_t)SW * M * sizeof(fz::Cand))));
-            if (lds2 <= 160 * 1024 && sblocks >= 1) {
+            if (lds2 <= FZ_LDS_BYTES && sblocks >= 1) {
                 HIPCHK(hipFuncSetAttribute((const void*)sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
                 hipLaunchKernelGGL(sweep, dim3((unsigned)sblocks), dim3(SW * 64), lds2, c->stream, src_in, c->d_kv.as<fz::KdeView>() + 1,
                                    kv_in.acc_stride, n, (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<fz::Cand>(), M, lmap, levid, pdfs,
@@ -304,7 +327,7 @@ constexpr bool fz_has_wspace() {
 inline bool& fz_exact_now() { static thread_local bool v = false; return v; }
 template <class SRC>
 bool fz_use_wspace(const SRC& src) {
-    if constexpr (fz_has_wspace<SRC>()) return src.lp.dim_prior && !fz_dbg("FZ_NO_WSPACE") && !fz_exact_now();
+    if constexpr (fz_has_wspace<SRC>()) return src.lp.dim_prior && !fz_dbg_set("FZ_NO_WSPACE") && !fz_exact_now();
     return false;
 }
 template <class SRC, int TW, int NW>
@@ -323,7 +346,7 @@ template <class SRC>
 double fz_nolist_probe(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n, int64_t M, const fz_kde_opts* ko) {
     if constexpr (!fz_has_wspace<SRC>()) return -1.0;
     else {
-        if (!src.lp.dim_prior || fz_dbg("FZ_NO_WSPACE") || kv.kmode != fz::KDE_HIST || !kv.normtab || !(ko->wt_thresh > 0.0)) return -1.0;
+        if (!src.lp.dim_prior || fz_dbg_set("FZ_NO_WSPACE") || kv.kmode != fz::KDE_HIST || !kv.normtab || !(ko->wt_thresh > 0.0)) return -1.0;
         const int S = 256;
         const double denom = (double)S * (double)((M + 255) / 256) * 64.0;
         if (!c->h_probe) {
@@ -370,22 +393,20 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
     {
         hipFuncAttributes fa;
         HIPCHK(hipFuncGetAttributes(&fa, (const void*)kern));
-        if (fa.sharedSizeBytes + lds > 160 * 1024) return 1;
+        if (fa.sharedSizeBytes + lds > FZ_LDS_BYTES) return 1;
     }
-    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int bpc = 1;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)kern, NW * 64, lds));
-    bpc = std::max(1, bpc);
     const int64_t groups = (n + TW - 1) / TW;
     const int64_t need = (groups + NW - 1) / NW;
+    int bpc = 1;
+    int64_t blocks = need;           // (what the helper answers while need <= CUs)
+    FZCHK(fz_resident_blocks(c, kern, NW * 64, lds, need, blocks, &bpc));
     // the ambiguous lists: a thin band of the candidates when the best model fits well (~1 % of M on the benchmark).  Sized at
     // M up to 131 072 models (can never overflow), M / 8 beyond (an object that overflows is re-run by the exact sweep): a
     // 1e6-model set then keeps the whole chip busy inside the workspace budget
     int64_t acap = (M <= 131072) ? M : std::max<int64_t>(131072, M / 8);
-    if (const char* e = fz_dbg("FZ_HIST_AMBCAP")) acap = std::max<int64_t>(1, atoll(e));      // (tests: forces the overflow hand-back)
+    if (fz_dbg_set("FZ_HIST_AMBCAP")) acap = std::max<int64_t>(1, fz_dbg_int("FZ_HIST_AMBCAP", 1));      // (tests: forces the overflow hand-back)
     const size_t per_wave = (size_t)TW * acap * sizeof(fz::Cand);
     const int64_t fit = (int64_t)(c->ws_limit / (per_wave * NW));
-    int64_t blocks = need;
     if (need > c->cu_count) {
         const int64_t k = std::min<int64_t>(bpc, fit / c->cu_count);
         if (k >= 1) blocks = std::min<int64_t>(need, k * c->cu_count);
@@ -402,7 +423,7 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
     {
         hipFuncAttributes fa;
         HIPCHK(hipFuncGetAttributes(&fa, (const void*)sweep));
-        if (fa.sharedSizeBytes + lds2 <= 160 * 1024) {
+        if (fa.sharedSizeBytes + lds2 <= FZ_LDS_BYTES) {
             HIPCHK(hipFuncSetAttribute((const void*)sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
             HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bps, (const void*)sweep, SW * 64, lds2));
             sweep_ok = true;
@@ -412,12 +433,9 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
     bps = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(bps, 4), (int64_t)(c->ws_limit / (sweep_blk * c->cu_count))));
     const size_t sweep_ws = (size_t)bps * c->cu_count * sweep_blk;
     if (c->d_cand.ensure(std::max((size_t)blocks * NW * per_wave, sweep_ws)) != 0) return 1;
-    FZCHK(c->d_kv.ensure(2 * sizeof(fz::KdeView)));
-    HIPCHK(hipMemcpyAsync(c->d_kv.p, &kv, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_kv.as<fz::KdeView>() + 1, &kvs, sizeof(fz::KdeView), hipMemcpyHostToDevice, c->stream));
     FZCHK(c->d_redo.ensure(((size_t)n + 1) * sizeof(int)));
     HIPCHK(hipMemsetAsync(c->d_redo.p, 0, sizeof(int), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));          // kv is a stack object
+    FZCHK(fz_upload_kv(c, kv, &kvs));
     Timer t(c, &c->tm.ms_fused, &c->tm.n_fused);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, src, c->d_kv.as<fz::KdeView>(), kv.acc_stride, n,
                        (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<fz::Cand>(), acap, lmap, levid, pdfs, c->omap, c->d_redo.as<int>());
@@ -444,7 +462,7 @@ int fz_launch_hist(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n, 
         const bool ex = exact || SRC::LMODE == 2;
         if constexpr (SRC::NB > 8) {
             // wide records: one object per wave, eight waves per block (up to 256 registers per lane)
-            if (fz_dbg("FZ_HIST_WIDE") && atoi(fz_dbg("FZ_HIST_WIDE")) == 0) return 1;      // (tests: the masked kernels of round 2)
+            if (fz_dbg_int("FZ_HIST_WIDE", 1) == 0) return 1;      // (tests: the masked kernels of round 2)
             if (ex) return fz_launch_hist_g<SRC, 1, 8, true>(c, src, kv, n, M, ko, lmap, levid, pdfs);
             return fz_launch_hist_g<SRC, 1, 8, false>(c, src, kv, n, M, ko, lmap, levid, pdfs);
         } else {
@@ -464,10 +482,10 @@ int fz_launch_hist_objmask(fz_ctx* c, const SRC& src, const SWS& sws, int64_t n,
     else {
         fz::KdeView kv;
         FZCHK(fz_kde_view(c, kv));
-        if (c->force_twopass || (fz_dbg("FZ_HIST") && atoi(fz_dbg("FZ_HIST")) == 0) || (fz_dbg("FZ_HIST_OBJMASK") && atoi(fz_dbg("FZ_HIST_OBJMASK")) == 0)) return 1;
+        if (c->force_twopass || fz_dbg_int("FZ_HIST", 1) == 0 || fz_dbg_int("FZ_HIST_OBJMASK", 1) == 0) return 1;
         // (every form of k_hist forms and sums its weights in fp64: a request for the exact evidence needs no other kernel)
         if (!(ko->wt_thresh > 0.0) || M >= ((int64_t)1 << 31) || kv.kmode != fz::KDE_HIST || !kv.normtab) return 1;
-        if (!src.lp.dim_prior && fz_dbg("FZ_HIST_NODIMPRIOR") && atoi(fz_dbg("FZ_HIST_NODIMPRIOR")) == 0) return 1;
+        if (!src.lp.dim_prior && fz_dbg_int("FZ_HIST_NODIMPRIOR", 1) == 0) return 1;
         fz_exact_now() = false;
         constexpr int NWH = SRC::NB > 8 ? 8 : 16;
         int r;
@@ -488,9 +506,9 @@ int fz_launch_hist_seg(fz_ctx* c, const SRC& src, const SWS& sws, int64_t n, int
     else {
         fz::KdeView kv0;
         FZCHK(fz_kde_view(c, kv0));
-        if (c->force_twopass || (fz_dbg("FZ_HIST") && atoi(fz_dbg("FZ_HIST")) == 0) || (fz_dbg("FZ_HIST_SEG") && atoi(fz_dbg("FZ_HIST_SEG")) == 0)) return 1;
+        if (c->force_twopass || fz_dbg_int("FZ_HIST", 1) == 0 || fz_dbg_int("FZ_HIST_SEG", 1) == 0) return 1;
         // one dictionary kernel (histogram + one convolution), or many through the class-ordered segments (one convolution per class)
-        const bool mcw = kv0.kmode == fz::KDE_DICT && c->mc_ok && !(fz_dbg("FZ_HIST_SEG_MC") && atoi(fz_dbg("FZ_HIST_SEG_MC")) == 0);
+        const bool mcw = kv0.kmode == fz::KDE_DICT && c->mc_ok && fz_dbg_int("FZ_HIST_SEG_MC", 1) != 0;
         if (!(ko->wt_thresh > 0.0) || M >= ((int64_t)1 << 31)) return 1;
         if (!mcw && (kv0.kmode != fz::KDE_HIST || !kv0.normtab)) return 1;
         // without the dimensionality prior the ln-like of mode A carries sum_b ln(xe^2 + ye^2) of the PAIR (pdf.py:96-98): not a power-0 form
@@ -512,10 +530,9 @@ int fz_launch_hist_seg(fz_ctx* c, const SRC& src, const SWS& sws, int64_t n, int
         fz_exact_now() = false;
         // direct form: the free scale always (fz_hist.h); broad likelihoods by the sampled share of pairs within the threshold (the
         // sample's mask-free arithmetic is an estimate here, which is all the choice needs); FZ_NOLIST=1 / 0 forces / forbids
-        bool ex = SRC::LMODE == 2 || (fz_dbg("FZ_EXACT_EVIDENCE") && atoi(fz_dbg("FZ_EXACT_EVIDENCE")) != 0);
+        bool ex = SRC::LMODE == 2 || fz_dbg_int("FZ_EXACT_EVIDENCE", 0) != 0;
         if (!ex) {
-            const char* e = fz_dbg("FZ_NOLIST");
-            const int want = e ? atoi(e) : -1;
+            const int want = (int)fz_dbg_int("FZ_NOLIST", -1);
             if (want < 0 && n >= 16384) ex = fz_nolist_probe<SRC>(c, src, kv0, n, M, ko) > 0.12;
             else ex = want == 1;
         }
@@ -541,9 +558,9 @@ template <class SRC>
 int fz_launch_hist_only(fz_ctx* c, const SRC& src, int64_t n, int64_t M, const fz_kde_opts* ko, double* lmap, double* levid, double* pdfs) {
     fz::KdeView kv;
     FZCHK(fz_kde_view(c, kv));
-    if (c->force_twopass || (fz_dbg("FZ_HIST") && atoi(fz_dbg("FZ_HIST")) == 0)) return 1;
+    if (c->force_twopass || fz_dbg_int("FZ_HIST", 1) == 0) return 1;
     // FZ_EXACT_EVIDENCE=1 (tests): the form that weighs every pair without classifying it first
-    const bool exact = fz_dbg("FZ_EXACT_EVIDENCE") && atoi(fz_dbg("FZ_EXACT_EVIDENCE")) != 0;
+    const bool exact = fz_dbg_int("FZ_EXACT_EVIDENCE", 0) != 0;
     fz_exact_now() = exact || c->exact_evidence;
     const int r = fz_launch_hist<SRC>(c, src, kv, n, M, ko, lmap, levid, pdfs, exact);
     if (r <= 0) c->last_form = (exact || SRC::LMODE == 2) ? "k_hist<exact>" : "k_hist<screen>";
@@ -563,18 +580,17 @@ int fz_launch_fitpredict(fz_ctx* c, const SRC& src, int64_t n, int64_t M, const 
         // the default where it applies: one pass, LDS histograms, no candidate lists, every weight and sum in fp64 (fz_hist.h); FZ_HIST=0
         // keeps k_fused, FZ_EXACT_EVIDENCE=1 (tests) the form that weighs every pair without classifying it first.  like_opts.exact_evidence
         // matters to k_fused's weight-space body only (fp32 remainder of the evidence there)
-        const bool exact = fz_dbg("FZ_EXACT_EVIDENCE") && atoi(fz_dbg("FZ_EXACT_EVIDENCE")) != 0;
+        const bool exact = fz_dbg_int("FZ_EXACT_EVIDENCE", 0) != 0;
         fz_exact_now() = exact || c->exact_evidence;
         double share = -2.0;                                     // not sampled yet
-        if (!fz_dbg("FZ_HIST") || atoi(fz_dbg("FZ_HIST")) != 0) {
+        if (fz_dbg_int("FZ_HIST", 1) != 0) {                     // (unset: on)
             // The classifier pays when it drops most pairs: with 7 % of the pairs within wt_thresh of the best (41 % above the drop
             // bar) it runs level with the form that weighs every pair directly (53.4 vs 54.9 ms per 2.6e10 pairs), with 3 % ahead of
             // it (46.0 vs 55.2); for broader likelihoods (faint data: the reference's own mock sits at 41 %; bench.py --noise-scale
             // 3 / 10: 53 % / 95 %) the direct form is the faster one.  FZ_NOLIST=1 / 0 forces / forbids the switch.
             bool broad = false;
             if (!exact) {
-                const char* e = fz_dbg("FZ_NOLIST");
-                const int want = e ? atoi(e) : -1;
+                const int want = (int)fz_dbg_int("FZ_NOLIST", -1);
                 if (want < 0 && n >= 16384) { share = fz_nolist_probe<SRC>(c, src, kv, n, M, ko); broad = share > 0.12; }
                 else broad = want == 1;
             }
@@ -600,9 +616,9 @@ int fz_launch_fitpredict(fz_ctx* c, const SRC& src, int64_t n, int64_t M, const 
             // 128 VGPRs, and the body then spills inside the model loop (3-4x slower); 12 waves (168 VGPRs) do not
             if (tw == 2 && nw == 16 && fz_use_wspace(src) && (SRC::LMODE == 0 || SRC::NB >= 7)) nw = 12;
             // ... and so does the class-sorted stack of many dictionary widths (its PDF stage keeps a 12-register result row)
-            if (tw == 2 && nw == 16 && fz_use_wspace(src) && kv.kmode == fz::KDE_DICT && c->mc_ok && !fz_dbg("FZ_NO_MC")) nw = 12;
+            if (tw == 2 && nw == 16 && fz_use_wspace(src) && kv.kmode == fz::KDE_DICT && c->mc_ok && !fz_dbg_set("FZ_NO_MC")) nw = 12;
             else if (tw == 4 && SRC::PREF_2x8) { tw = 2; nw = 8; }
-            if (const char* e = fz_dbg("FZ_FUSED_CFG")) sscanf(e, "%d,%d", &tw, &nw);
+            if (fz_dbg_set("FZ_FUSED_CFG")) sscanf(fz_dbg_str("FZ_FUSED_CFG").c_str(), "%d,%d", &tw, &nw);
             if (tw == 4 && nw == 8) r = fz_launch_fused_tw<SRC, 4, 8>(c, src, kv, n, M, ko, lmap, levid, pdfs);
             else if (tw == 2 && nw == 8) r = fz_launch_fused_tw<SRC, 2, 8>(c, src, kv, n, M, ko, lmap, levid, pdfs);
             else if (tw == 2 && nw == 16) r = fz_launch_fused_tw<SRC, 2, 16>(c, src, kv, n, M, ko, lmap, levid, pdfs);

@@ -204,8 +204,11 @@ def test_switches_reach_the_library_through_one_call(monkeypatch):
     before a call whenever they have changed (include/frankenz_hip.h)"""
     from frankenz_amd import _lib
     lib = _lib.load()
-    src = open(os.path.join(ROOT, 'frankenz_amd', 'csrc', 'frankenz_hip.hip')).read() + open(os.path.join(ROOT, 'frankenz_amd', 'csrc', 'fz_launch.h')).read()
-    assert 'getenv(' not in src
+    csrc = os.path.join(ROOT, 'frankenz_amd', 'csrc')                # every source of the library, wherever host code lives
+    srcs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h', '.inc'))]
+    assert os.path.join(csrc, 'frankenz_hip.hip') in srcs and os.path.join(csrc, 'fz_launch.h') in srcs and len(srcs) > 20
+    for path in srcs + [os.path.join(ROOT, 'tools', 'dev_stubs.hip')]:
+        assert 'getenv(' not in open(path).read(), path
     monkeypatch.setenv('FZ_ABI_TEST_SWITCH', '7')
     lib.fz_device_count()                           # any entry point: the set is synchronised first
     assert 'FZ_ABI_TEST_SWITCH=7' in lib._sent
