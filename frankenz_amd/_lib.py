@@ -104,6 +104,8 @@ ABI = {
     "fz_net_stack": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I64, _I64, _P, _P, _P]),
     "fz_som_train": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I64, _I32, _I32, _F64, _F64,
                                C.POINTER(LikeOpts), _I32, _I64, _I64, _P]),
+    "fz_gng_train": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64,
+                               _F64, _F64, _F64, _F64, C.POINTER(LikeOpts), _I32, _I64, _I64, _I64, _I64, _P, _P]),
     "fz_knn_search_fit_predict_prior": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F64, _F64, C.POINTER(LikeOpts),
                                                   C.POINTER(KdeOpts), C.POINTER(Prior)] + [_P] * 12),
     "fz_knn_fit_predict_prior": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, C.POINTER(LikeOpts),

@@ -13,6 +13,7 @@
 #include "fz_summary.h"
 #include "fz_net.h"
 #include "fz_som.h"
+#include "fz_gng.h"
 #include "fz_nzmc.h"
 
 using namespace fz;
@@ -1171,6 +1172,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_summary_host.inc"
 #include "fz_net_host.inc"
 #include "fz_som_host.inc"
+#include "fz_gng_host.inc"
 #include "fz_nzmc_host.inc"
 
 #ifdef FZ_KM_STATS

@@ -357,6 +357,17 @@ class Engine(object):
                                     ptr(draws), ptr(lr), ptr(sig), int(len(draws)), int(kind), int(bool(use_wt)), float(wt_thresh),
                                     float(cdf_thresh), C.byref(opts), int(bool(track_scale)), int(s0), int(s1), ptr(bmus)))
 
+    def gng_train(self, x, xe, xm, draws, fstate, istate, ids, cap, max_degree, prune_cap, edge_cap, nbatch, max_age, max_nodes,
+                  nnode_init, learn_best, learn_neighbor, new_err_keep, all_err_keep, opts, track_scale, alias0, alias1, s0, s1, bmus,
+                  batch):
+        """steps [s0, s1) of GNG training (fz_gng_train); arrays are NumPy or torch tensors on this engine's GPU"""
+        M, B = x.shape
+        check(self.lib.fz_gng_train(self.h, ptr(x), ptr(xe), ptr(xm), int(M), int(B), ptr(draws), int(len(draws)), ptr(fstate),
+                                    ptr(istate), ptr(ids), int(cap), int(max_degree), int(prune_cap), int(edge_cap), int(nbatch),
+                                    int(max_age), int(max_nodes), int(nnode_init), float(learn_best), float(learn_neighbor),
+                                    float(new_err_keep), float(all_err_keep), C.byref(opts), int(bool(track_scale)), int(alias0),
+                                    int(alias1), int(s0), int(s1), ptr(bmus), ptr(batch)))
+
     def pdfs_summarize(self, pdfs, pgrid, renormalize, urand, loss, widths, wscale, stats, n=None):
         n = len(pdfs) if n is None else n
         check(self.lib.fz_pdfs_summarize(self.h, ptr(pdfs), n, len(pgrid), ptr(pgrid), int(bool(renormalize)),

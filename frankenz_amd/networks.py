@@ -1,6 +1,7 @@
 """
 Inference through a trained network (SOM / GNG): the reference's ``_Network`` (frankenz/networks.py:120-1473), and
-the training of a ``SelfOrganizingMap`` on the device (networks.py:1490-1867, ``fz_som_train``, docs/som.md, at the end of this file).
+the training of a ``SelfOrganizingMap`` (networks.py:1490-1867, ``fz_som_train``, docs/som.md) and of a ``GrowingNeuralGas``
+(networks.py:1870-2260, ``fz_gng_train``, docs/gng.md) on the device, at the end of this file.
 The network is DATA here -- node positions in data space -- and everything the reference then does with it runs
 through the library:
 
@@ -23,7 +24,7 @@ import numpy as np
 from . import pdf as _pdf
 from .engine import HostObjects, get_engine, kde_opts, like_opts, merge_kde_args
 
-__all__ = ["populate_network", "Network", "SelfOrganizingMap", "learn_linear", "learn_geometric", "learn_harmonic",
+__all__ = ["populate_network", "Network", "SelfOrganizingMap", "GrowingNeuralGas", "learn_linear", "learn_geometric", "learn_harmonic",
            "neighbor_gauss", "neighbor_lorentz"]
 
 _NET_CHUNK = 1 << 16          # objects per device call
@@ -719,3 +720,319 @@ def _som_device_arrays(device, arrays):
         return arrays
     d = torch.device('cuda', device)
     return tuple(torch.from_numpy(a).to(d) for a in arrays)
+
+
+# ---- training of a growing neural gas (reference networks.py:1870-2260) --------------------------------------------------------------
+# The network is kept as plain arrays -- labels, positions, errors, ordered adjacency lists, edge ages -- on the device
+# (fz_gng_train, docs/gng.md) and in the host loop alike; networkx is needed only for ``self.graph`` and ``graph_init``.
+
+_GNG_MAX_DEGREE = 64          # neighbours per node the device's adjacency lists hold (the default-size reference run peaks at 18)
+_GNG_MAX_NODES = 65536        # max(max_nodes, initial nodes) the device path takes (FZ_GNG_MAX_NODES)
+_GNG_SEGMENT = 10000          # training steps per kernel launch (the network stays on the device between launches)
+_GNG_NCNT = 16                # counters at the head of the integer state (include/frankenz_hip.h)
+
+
+def _gng_state_sizes(cap, B, md, pcap, ecap):
+    """(doubles, int32s) of the two state arrays of fz_gng_train"""
+    return 2 * cap * B + cap + 2 * B, _GNG_NCNT + 2 * cap + 4 * cap * md + 3 * pcap + ecap
+
+
+def _gng_read_graph(graph):
+    """a networkx-style graph with ``pos``, ``error`` and ``age`` attributes -> labels, positions (the graph's own arrays), errors
+    and per-node neighbour labels / ages, in the graph's node and adjacency order"""
+    ids = list(graph.nodes())
+    pos = [graph.nodes[n]['pos'] for n in ids]
+    err = [graph.nodes[n]['error'] for n in ids]
+    nbrs = [list(graph.neighbors(n)) for n in ids]
+    ages = [[graph.edges[n, m]['age'] for m in nb] for n, nb in zip(ids, nbrs)]
+    return ids, pos, err, nbrs, ages
+
+
+def _gng_fill_graph(graph, ids, pos, err, off, nbr, age):
+    """the arrays -> ``graph`` (emptied first): node attributes ``pos``, ``error``, ``count``, edge attribute ``age``, nodes and every
+    node's neighbours in the given order.  The adjacency is written directly (``graph._adj``): no sequence of ``add_edge`` calls
+    is known that leaves every node's neighbours in a prescribed order."""
+    graph.clear()
+    for k, n in enumerate(ids):
+        graph.add_node(n, pos=pos[k], error=err[k], count=k)
+    attrs = {}
+    for k, n in enumerate(ids):
+        for j in range(off[k], off[k + 1]):
+            m = ids[nbr[j]]
+            key = (k, nbr[j]) if k < nbr[j] else (nbr[j], k)
+            if key not in attrs:
+                attrs[key] = {'age': int(age[j])}
+            graph._adj[n][m] = attrs[key]
+    return graph
+
+
+class GrowingNeuralGas(Network):
+    """The reference's ``GrowingNeuralGas``: ``train_network`` runs on the device (``fz_gng_train``, one persistent workgroup per
+    network, docs/gng.md); inference is the inherited ``Network``.  After training the network is held as plain arrays, in the
+    reference's node order: ``graph_ids`` (labels), ``graph_pos`` (NNODE, Nfilt), ``graph_errors``, and the adjacency in neighbour
+    order as CSR -- ``graph_adj_off`` (NNODE + 1), ``graph_adj_nbr`` (node indices), ``graph_adj_age``.  ``graph`` is the same
+    network as a ``networkx.Graph`` with the reference's attributes (``pos``, ``error``, ``count``; ``age``), or None where networkx
+    is not installed."""
+
+    def __init__(self, models, models_err, models_mask, device=None):
+        super(GrowingNeuralGas, self).__init__(models, models_err, models_mask, device=device)
+        self.graph = _new_graph()
+        self.graph_ids = self.graph_pos = self.graph_errors = self.graph_adj_off = self.graph_adj_nbr = self.graph_adj_age = None
+
+    def train_network(self, models=None, models_err=None, models_mask=None, learn_best=0.2, learn_neighbor=0.005, max_age=15,
+                      nbatch=50, new_err_dec=0.5, all_err_dec=5e-3, max_nodes=2500, niter=5000, graph_init=None, err_kernel=None,
+                      lprob_func=None, rstate=None, lprob_args=None, lprob_kwargs=None, track_scale=False, verbose=True):
+        """Grow a network of at most ``max_nodes`` nodes on the models (by default the ones the object was built with) over
+        ``niter * nbatch`` steps.  Keywords and defaults are the reference's (networks.py:1898-2035); afterwards ``nodes``,
+        ``NNODE``, ``graph`` and the ``graph_*`` arrays hold the trained network."""
+        models = _given(models, self.models)
+        models_err = _given(models_err, self.models_err)
+        models_mask = _given(models_mask, self.models_mask)
+        if err_kernel is not None:
+            models_err = np.sqrt(models_err**2 + err_kernel**2)          # added in quadrature
+        steps = self._train_network(models, models_err, models_mask, learn_best=learn_best, learn_neighbor=learn_neighbor,
+                                    max_age=max_age, nbatch=nbatch, new_err_dec=new_err_dec, all_err_dec=all_err_dec,
+                                    max_nodes=max_nodes, niter=niter, graph_init=graph_init, lprob_func=lprob_func, rstate=rstate,
+                                    lprob_args=lprob_args, lprob_kwargs=lprob_kwargs, track_scale=track_scale)
+        for i, (_, _, nnodes, nprune) in enumerate(steps):
+            if i % nbatch == 0 and verbose:                               # once per batch, the reference's progress line
+                sys.stderr.write('\rIteration {0}/{1} [nodes={2}, edges pruned={3}] '.format(int(i / nbatch) + 1, niter, nnodes, nprune))
+                sys.stderr.flush()
+        if verbose:
+            sys.stderr.write('\n')
+            sys.stderr.flush()
+
+    def _train_network(self, models, models_err, models_mask, learn_best=0.2, learn_neighbor=0.005, max_age=15, nbatch=50,
+                       new_err_dec=0.5, all_err_dec=5e-3, max_nodes=2500, niter=5000, graph_init=None, lprob_func=None, rstate=None,
+                       lprob_args=None, lprob_kwargs=None, track_scale=False, verbose=True):
+        """Generator of the training steps, ``(node_results, bmu, NNODE, nprune)`` each.  On the device path ``node_results`` is
+        None: the (T, Nnode) likelihood rows are never formed (docs/deviations.md)."""
+        lprob_func = _given(lprob_func, _pdf.logprob)
+        lprob_args = _given(lprob_args, [])
+        lprob_kwargs = _given(lprob_kwargs, {'free_scale': True, 'ignore_model_err': True})
+        rstate = _given(rstate, np.random)
+        Nmodel, B = len(models), np.shape(models)[1]
+        T = int(niter) * int(nbatch)
+        nbatches = (T - 1) // nbatch + 1 if T > 0 else 0
+        device = _is_default(lprob_func) and not lprob_args
+        nn0 = 2 if graph_init is None else graph_init.number_of_nodes()
+        if device:
+            # the device path's limits, refused before anything is drawn or touched
+            if B > 32:
+                raise NotImplementedError("GrowingNeuralGas.train_network: %d bands unsupported on the device (at most 32)" % B)
+            if max(int(max_nodes), nn0) > _GNG_MAX_NODES:
+                raise NotImplementedError("GrowingNeuralGas.train_network: max(max_nodes, initial nodes) = %d unsupported on the "
+                                          "device (at most %d)" % (max(int(max_nodes), nn0), _GNG_MAX_NODES))
+            if T >= 1 << 30:
+                raise NotImplementedError("GrowingNeuralGas.train_network: %d steps unsupported on the device (below 2**30)" % T)
+            opts = like_opts(lprob_kwargs)
+            if track_scale and not (opts.free_scale and lprob_kwargs.get('return_scale', False)):
+                raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True, return_scale=True)")
+        if nn0 < 2:
+            raise ValueError("graph_init needs at least two nodes")
+
+        if graph_init is None:
+            i1, i2 = (int(v) for v in rstate.choice(Nmodel, size=2, replace=False))
+            ids, pos, err = [0, 1], [models[i1], models[i2]], [0., 0.]    # the positions are views: training rewrites the two rows
+            nbrs, ages = [[1], [0]], [[0], [0]]
+            alias = (i1, i2)
+        else:
+            ids, pos, err, nbrs, ages = _gng_read_graph(graph_init)
+            alias = (-1, -1)
+            taken = set(ids)
+            clash = [nn0 + k for k in range(nbatches) if nn0 + k in taken]
+            if clash:
+                # (the reference would silently overwrite that node's position and error with the new node's)
+                raise ValueError("graph_init: the label %r of a node to be inserted is already in the graph" % (clash[0],))
+        self.NNODE = nn0
+
+        if device and graph_init is None:
+            rows = np.array(alias)
+            cx, ce = np.asarray(models[rows], dtype=np.float64), np.asarray(models_err[rows], dtype=np.float64)
+            if not (np.isfinite(cx) & np.isfinite(ce) & (ce > 0.)).all():
+                device = False           # cleaning such a row would reach into a node's position mid-run: the host loop does just that
+        if not device:
+            for step in self._gng_host_steps(ids, pos, err, nbrs, ages, models, models_err, models_mask, rstate, lprob_func, lprob_args,
+                                             lprob_kwargs, learn_best, learn_neighbor, max_age, nbatch, new_err_dec, all_err_dec,
+                                             max_nodes, T, track_scale, nn0, graph_init):
+                yield step
+            return
+
+        draws = _draw_stream(rstate, Nmodel, T)
+        # the models cleaned up front (pdf.py:309-311), the drawn rows of the caller's arrays too, as in the SOM path
+        x, xe = np.array(models, dtype=np.float64, order='C'), np.array(models_err, dtype=np.float64, order='C')
+        xm = np.array(models_mask, dtype=np.float64, order='C')
+        _clean_rows(x, xe, xm, np.arange(Nmodel))
+        _clean_rows(models, models_err, models_mask, np.unique(draws))
+        # ---- the state arrays (include/frankenz_hip.h) ----
+        md = int(_GNG_MAX_DEGREE)
+        cap = max(int(max_nodes), nn0)
+        if max(len(v) for v in nbrs) > md:
+            raise RuntimeError("graph_init: a node has more than %d neighbours (networks._GNG_MAX_DEGREE)" % md)
+        slot = {n: k for k, n in enumerate(ids)}
+        edge, adj = {}, np.zeros((2, cap, md, 2), dtype=np.int32)
+        deg = np.zeros(cap, dtype=np.int32)
+        edge_age = []
+        for k, (nb, ag) in enumerate(zip(nbrs, ages)):
+            deg[k] = len(nb)
+            for j, (m, a_) in enumerate(zip(nb, ag)):
+                key = (k, slot[m]) if k < slot[m] else (slot[m], k)
+                if key not in edge:
+                    edge[key] = len(edge_age); edge_age.append(int(a_))
+                adj[0, k, j] = (slot[m], edge[key])
+        pcap = max(2, min(int(nbatch) * md, 1 << 22))
+        ecap = len(edge_age) + T + 2 * nbatches + 8
+        nf, ni = _gng_state_sizes(cap, B, md, pcap, ecap)
+        fst, ist = np.zeros(nf), np.zeros(ni, dtype=np.int32)
+        p0 = np.array([np.asarray(p, dtype=np.float64) for p in pos])
+        if p0.shape != (nn0, B):
+            raise ValueError("graph_init: every node needs a position of %d values" % B)
+        fst[:nn0 * B] = p0.ravel(); fst[cap * B:cap * B + nn0 * B] = p0.ravel()
+        fst[2 * cap * B:2 * cap * B + nn0] = err
+        if alias[0] >= 0:
+            fst[2 * cap * B + cap:] = p0[:2].ravel()
+        ist[:8] = [nn0, 0, len(edge_age), 0, 0, 0 if alias[0] >= 0 else -1, 1 if alias[0] >= 0 else -1, 0]
+        o_adj = _GNG_NCNT + 2 * cap
+        o_age = o_adj + 4 * cap * md + 3 * pcap
+        ist[_GNG_NCNT:_GNG_NCNT + cap] = deg
+        ist[o_adj:o_adj + 4 * cap * md] = adj.ravel()
+        ist[o_age:o_age + len(edge_age)] = edge_age
+        idv = np.zeros(cap, dtype=np.int64); idv[:nn0] = ids
+        bmus, batch = np.zeros(max(T, 1), dtype=np.int64), np.zeros((max(nbatches, 1), 2), dtype=np.int32)
+        eng = self._eng()
+        dev = _som_device_arrays(eng.device, (x, xe, xm, draws, fst, ist, idv, bmus, batch))
+        dx, dxe, dxm, ddraws, dfst, dist, dids, dbmus, dbatch = dev
+        host = lambda a_: a_ if isinstance(a_, np.ndarray) else a_.cpu().numpy()
+        seg = max(1, int(_GNG_SEGMENT))
+        for s0 in range(0, T, seg):
+            s1 = min(T, s0 + seg)
+            eng.gng_train(dx, dxe, dxm, ddraws, dfst, dist, dids, cap, md, pcap, ecap, nbatch, max_age, max_nodes, nn0, learn_best,
+                          learn_neighbor, 1. - new_err_dec, 1. - all_err_dec, opts, track_scale, alias[0], alias[1], s0, s1, dbmus,
+                          dbatch)
+            bm, bt = host(dbmus[s0:s1]), host(dbatch)
+            f, i_, idh = host(dfst), host(dist), host(dids)
+            NN, cur = int(i_[0]), int(i_[7])
+            dg = i_[_GNG_NCNT:_GNG_NCNT + NN]
+            ad = i_[o_adj:o_adj + 4 * cap * md].reshape(2, cap, md, 2)[cur, :NN]
+            keep = np.arange(md)[None, :] < dg[:, None]
+            off = np.zeros(NN + 1, dtype=np.int64); np.cumsum(dg, out=off[1:])
+            gpos = f[:cap * B].reshape(cap, B)[:NN].copy()
+            fit = f[cap * B:2 * cap * B].reshape(cap, B)[:NN].copy() if track_scale else gpos.copy()
+            plist = [p for p in gpos]
+            if alias[0] >= 0:
+                # the two rows the initial nodes were views of: what the nodes hold now (or held when they were removed)
+                rows_now = f[2 * cap * B + cap:].reshape(2, B)
+                for k in range(2):
+                    models[alias[k]] = rows_now[k]
+                    if i_[5 + k] >= 0 and isinstance(models, np.ndarray):
+                        plist[int(i_[5 + k])] = models[alias[k]]
+            self._gng_finish([int(v) for v in idh[:NN]], plist, gpos, f[2 * cap * B:2 * cap * B + NN].copy(), off, ad[..., 0][keep],
+                             i_[o_age:][ad[..., 1][keep]], fit, graph_init)
+            for i in range(s0, s1):
+                yield None, int(bm[i - s0]), int(bt[i // nbatch, 0]), int(bt[i // nbatch, 1])
+
+    def _gng_finish(self, ids, pos_list, pos, err, off, nbr, age, fit, graph_init):
+        """the trained network into the attributes (class docstring); ``graph_init`` is refilled in place, as the reference trains it"""
+        self.graph_ids, self.graph_pos, self.graph_errors = np.array(ids), pos, np.asarray(err, dtype=np.float64)
+        self.graph_adj_off, self.graph_adj_nbr = np.asarray(off, dtype=np.int64), np.asarray(nbr, dtype=np.int64)
+        self.graph_adj_age = np.asarray(age, dtype=np.int64)
+        self.nodes, self.NNODE = fit, len(ids)
+        graph = graph_init if graph_init is not None else _new_graph()
+        if graph is not None:
+            _gng_fill_graph(graph, ids, pos_list, [float(e) for e in err], self.graph_adj_off, self.graph_adj_nbr, self.graph_adj_age)
+        self.graph = graph
+
+    def _gng_host_steps(self, ids, pos, err, nbrs, ages, models, models_err, models_mask, rstate, lprob_func, lprob_args, lprob_kwargs,
+                        learn_best, learn_neighbor, max_age, nbatch, new_err_dec, all_err_dec, max_nodes, T, track_scale, nn0,
+                        graph_init):
+        """The reference's loop (networks.py:2158-2260) with the user's likelihood, on ordered dictionaries in place of the networkx
+        graph: ``nodes[label] = [pos, error]`` in node order, ``adj[label][neighbour] = [age]`` in neighbour order (the age cell is
+        shared by the two directions of an edge).  Positions are updated in place, so the two initial nodes keep rewriting the
+        caller's rows they are views of."""
+        import heapq
+        nodes = {n: [p, e] for n, p, e in zip(ids, pos, err)}
+        adj = {n: {} for n in ids}
+        for n, nb, ag in zip(ids, nbrs, ages):
+            for m, a_ in zip(nb, ag):
+                adj[n][m] = adj[m][n] if n in adj[m] else [a_]
+        order = list(nodes)
+        count = {n: k for k, n in enumerate(order)}
+        y = np.array([nodes[n][0] for n in order])
+        self.nodes = y
+        prune, nprune = [], 0
+        Nmodel = len(models)
+        for i in range(T):
+            idx = rstate.choice(Nmodel)
+            x, xe, xm = models[idx], models_err[idx], models_mask[idx]
+            res = lprob_func(x, xe, xm, y, np.zeros_like(y), np.ones_like(y, dtype='bool'), *lprob_args, **lprob_kwargs)
+            lnp, chi2 = res[2], res[4]
+            if track_scale:
+                y *= res[5][:, None]                                      # the fit copy is rescaled, the graph positions are not
+            yb, yb2 = heapq.nlargest(2, range(len(lnp)), key=lnp.__getitem__)
+            bmu, bmu2 = order[yb], order[yb2]
+            resid = x - nodes[bmu][0]
+            y[yb] += learn_best * resid
+            nodes[bmu][0] += learn_best * resid
+            nodes[bmu][1] += chi2[yb]
+            if bmu2 in adj[bmu]:
+                adj[bmu][bmu2][0] = 0
+            else:
+                adj[bmu][bmu2] = adj[bmu2][bmu] = [0]
+            for n in list(adj[bmu]):
+                resid = x - nodes[n][0]
+                y[count[n]] += learn_neighbor * resid
+                nodes[n][0] += learn_neighbor * resid
+                cell = adj[bmu][n]
+                cell[0] += 1
+                if cell[0] == max_age:
+                    prune.append((bmu, n))
+            if i % nbatch == 0:
+                nprune = len(prune)
+                for e1, e2 in prune:
+                    if e1 in adj and e2 in adj[e1]:
+                        del adj[e1][e2], adj[e2][e1]
+                        for e in (e1, e2):
+                            if not adj[e]:
+                                del adj[e], nodes[e]
+                prune = []
+                if len(nodes) < max_nodes:
+                    keys = list(nodes)
+                    e1 = keys[int(np.argmax([nodes[n][1] for n in keys]))]
+                    e1_nbrs = list(adj[e1])
+                    e2 = e1_nbrs[int(np.argmax([nodes[n][1] for n in e1_nbrs]))]
+                    nodes[e1][1] *= (1. - new_err_dec)
+                    nodes[e2][1] *= (1. - new_err_dec)
+                    new = nn0 + int(i / nbatch)
+                    nodes[new] = [0.5 * (nodes[e1][0] + nodes[e2][0]), nodes[e1][1]]
+                    del adj[e1][e2], adj[e2][e1]
+                    adj[new] = {}
+                    adj[new][e1] = adj[e1][new] = [0]
+                    adj[new][e2] = adj[e2][new] = [0]
+                order = list(nodes)
+                count = {n: k for k, n in enumerate(order)}
+                y = np.array([nodes[n][0] for n in order])
+                self.nodes, self.NNODE = y, len(order)
+            for n in nodes:
+                nodes[n][1] *= (1. - all_err_dec)
+            if i == T - 1:
+                self._gng_publish(nodes, adj, y, graph_init)
+            yield res, bmu, len(order), nprune
+
+    def _gng_publish(self, nodes, adj, y, graph_init):
+        order = list(nodes)
+        count = {n: k for k, n in enumerate(order)}
+        off = np.zeros(len(order) + 1, dtype=np.int64)
+        np.cumsum([len(adj[n]) for n in order], out=off[1:])
+        nbr = [count[m] for n in order for m in adj[n]]
+        age = [adj[n][m][0] for n in order for m in adj[n]]
+        plist = [nodes[n][0] for n in order]
+        self._gng_finish(order, plist, np.array(plist, dtype=np.float64), [nodes[n][1] for n in order], off, nbr, age, y, graph_init)
+
+
+def _new_graph():
+    """an empty networkx.Graph, or None without networkx"""
+    try:
+        import networkx as nx
+    except ImportError:
+        return None
+    return nx.Graph()

@@ -322,6 +322,34 @@ int  fz_som_train(fz_ctx* ctx, const double* models, const double* models_err, c
                   double wt_thresh, double cdf_thresh, const fz_like_opts* opts, int32_t track_scale, int64_t s0, int64_t s1,
                   int32_t* bmus);
 
+/* ---- training of a growing neural gas (networks.py:1870-2260, GrowingNeuralGas.train_network) ----
+ * fz_gng_train -- steps [s0, s1) of the sequential training loop, batch ends included, run by ONE persistent workgroup
+ * (docs/gng.md).  Step i draws row draws[i] of the CLEANED models (as fz_som_train), takes its ln-probability against every live node,
+ * writes the label of the best node to bmus[i] (heapq.nlargest order: ties to the earlier node, nan ln-probs lowest), moves it by
+ * learn_best and its graph neighbours by learn_neighbor towards the row, adds the step's chi2 to its error, resets or creates the edge
+ * to the second-best node, ages the best node's edges and lists those whose age equals max_age.  Every step i with i % nbatch == 0
+ * ends a batch: batch[2 k + 1] (k = i / nbatch) = the number of listed edges; listed edges and nodes left without edges are removed;
+ * if fewer than max_nodes nodes live, a node labelled nnode_init + k is inserted between the node of the largest error and that
+ * node's neighbour of the largest error (both errors *= new_err_keep); batch[2 k] = live nodes.  Then every error *= all_err_keep.
+ * The network is the caller's state, read and written, in slot order = the reference's node order:
+ *   fstate  doubles: pos[cap * B] | fit[cap * B] (the rescaled copy of track_scale) | err[cap] | alias_rows[2 * B]
+ *   istate  int32:   counters[16] = {live nodes, prune entries, edge ids handed out, status, step of the status, slot of the node that
+ *                    is model row alias0 (-1: removed), the same for alias1, current adjacency buffer (0 / 1), 0...} |
+ *                    degree[cap] | aux[cap] (zero) | adjacency[2][cap * max_degree] pairs (neighbour slot, edge id), neighbour order |
+ *                    prune list[prune_cap] triples | age[edge_cap] by edge id
+ *   ids     int64[cap]: node labels.
+ * alias0 / alias1 (-1: none): model rows that ARE the positions of two nodes (the reference's initial nodes are views of the caller's
+ * rows): a draw of such a row reads the node's current position; alias_rows holds what the two rows hold after the call.
+ * Calling with consecutive ranges gives bit-identical state to one call over their union.  A node that would get more than
+ * max_degree neighbours stops the run: the call fails and names the limit.  B <= 32, cap <= FZ_GNG_MAX_NODES, 2 <= max_degree <= 64,
+ * T < 2^30; edge_cap >= initial edges + T + 2 * batch ends. */
+#define FZ_GNG_MAX_NODES 65536
+int  fz_gng_train(fz_ctx* ctx, const double* models, const double* models_err, const double* models_mask, int64_t M, int32_t B,
+                  const int64_t* draws, int64_t T, double* fstate, int32_t* istate, int64_t* ids, int32_t cap, int32_t max_degree,
+                  int32_t prune_cap, int32_t edge_cap, int32_t nbatch, int32_t max_age, int32_t max_nodes, int64_t nnode_init,
+                  double learn_best, double learn_neighbor, double new_err_keep, double all_err_keep, const fz_like_opts* opts,
+                  int32_t track_scale, int64_t alias0, int64_t alias1, int64_t s0, int64_t s1, int64_t* bmus, int32_t* batch);
+
 /* ---- device memory that outlives a call (the samplers' resident PDF stack and per-object state) ----
  * fz_dev_alloc / fz_dev_free: plain device allocations on the context's GPU.  fz_dev_copy: `bytes` from src to dst, either side in
  * host or device memory, complete on return. */
