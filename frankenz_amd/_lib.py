@@ -39,6 +39,10 @@ class Prior(C.Structure):
     _fields_ = [("table", C.c_void_p), ("P", C.c_int64), ("rows", C.c_void_p)]
 
 
+class PriorLerp(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("P", C.c_int64), ("rows", C.c_void_p), ("frac", C.c_void_p)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_planes", C.c_double), ("n_planes", C.c_int64),
                 ("ms_fused", C.c_double), ("n_fused", C.c_int64),
@@ -110,6 +114,14 @@ ABI = {
                                                   C.POINTER(KdeOpts), C.POINTER(Prior)] + [_P] * 12),
     "fz_knn_fit_predict_prior": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, C.POINTER(LikeOpts),
                                            C.POINTER(KdeOpts), C.POINTER(Prior)] + [_P] * 12),
+    "fz_fit_prior_lerp": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts), C.POINTER(PriorLerp)] + [_P] * 7),
+    "fz_fit_predict_prior_lerp": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts),
+                                            C.POINTER(KdeOpts), C.POINTER(PriorLerp), _P, _P, _P]),
+    "fz_knn_search_fit_predict_prior_lerp": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F64, _F64, C.POINTER(LikeOpts),
+                                                       C.POINTER(KdeOpts), C.POINTER(PriorLerp)] + [_P] * 12),
+    "fz_knn_fit_predict_prior_lerp": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, C.POINTER(LikeOpts),
+                                                C.POINTER(KdeOpts), C.POINTER(PriorLerp)] + [_P] * 12),
+    "fz_prior_rows_from_grid": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

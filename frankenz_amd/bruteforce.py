@@ -8,8 +8,8 @@ Same constructor, methods (``fit / predict / fit_predict`` and the generator twi
 fit_scale_err, NMODEL, NDIM, NDATA``), return shapes and dtypes.
 
 ``lprob_func`` may be ``None`` or this package's ``logprob`` (the reference default,
-bruteforce.py:105-106), or a ``pdf.logprob_prior`` instance (default likelihood plus
-an additive ln-prior table evaluated on the device): those run on the GPU end to end.
+bruteforce.py:105-106), or a ``pdf.logprob_prior`` / ``pdf.logprob_prior_lerp`` instance (default likelihood
+plus an additive ln-prior table evaluated on the device): those run on the GPU end to end.
 Any other callable -- the reference's plugin hook, bruteforce.py:193-194, e.g. demos/2's
 ``lprob_bpz`` -- is the USER's code: it is called once per object on the host exactly as
 the reference calls it (same arguments, ``lprob_args`` / ``lprob_kwargs`` included), its
@@ -45,9 +45,9 @@ class _HostFunc(object):
 
 
 def _check_lprob(lprob_func, lprob_args, Nmodel=None, lprob_kwargs=None):
-    """-> ``(prior, host)``: the ``logprob_prior`` to apply on the device (or None), and the
+    """-> ``(prior, host)``: the ``logprob_prior`` / ``logprob_prior_lerp`` to apply on the device (or None), and the
     per-object host callable (or None when the device computes the likelihood)."""
-    if isinstance(lprob_func, _pdf.logprob_prior):
+    if isinstance(lprob_func, (_pdf.logprob_prior, _pdf.logprob_prior_lerp)):
         if lprob_args:
             raise NotImplementedError("positional `lprob_args` are not supported with logprob_prior; use `lprob_kwargs`")
         if Nmodel is not None and lprob_func.M != Nmodel:

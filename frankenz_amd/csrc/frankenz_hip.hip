@@ -774,6 +774,25 @@ __global__ void k_prior_check(const int64_t* rows, int64_t n, int64_t P, int* fl
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (rows[i] < 0 || rows[i] >= P)) atomicExch(flag, 1);
 }
+// interpolated form: object i reads rows[i] and rows[i] + 1 -- rows in [0, P - 2], weights in [0, 1] (a nan weight fails the test)
+__global__ void k_prior_check_lerp(const int64_t* rows, const double* frac, int64_t n, int64_t P, int* flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (rows[i] < 0 || rows[i] > P - 2 || !(frac[i] >= 0.0 && frac[i] <= 1.0))) atomicExch(flag, 1);
+}
+// fz_prior_rows_from_grid: T[r][j] = (1 - g_j) V[r][iz_j][t_j] + g_j V[r][iz_j + 1][t_j]; one thread per (r, j), j fastest (the
+// stores of a wave are one 512-byte run; its reads gather V[r], which is one row's worth of cache lines)
+__global__ void k_prior_rows_from_grid(const double* __restrict__ V, int64_t P, int64_t NZ, int64_t NT, const int32_t* __restrict__ iz,
+                                       const double* __restrict__ g, const int32_t* __restrict__ t, int64_t M, double* __restrict__ T) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = blockIdx.y;
+    if (j >= M || r >= P) return;
+    const double* v = V + (r * NZ + iz[j]) * NT + t[j];
+    T[r * M + j] = prior_lerp(v[0], v[NT], g[j]);
+}
+__global__ void k_prior_grid_check(const int32_t* iz, const double* g, const int32_t* t, int64_t M, int64_t NZ, int64_t NT, int* flag) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < M && (iz[j] < 0 || iz[j] > NZ - 2 || t[j] < 0 || t[j] >= NT || !(g[j] >= 0.0 && g[j] <= 1.0))) atomicExch(flag, 1);
+}
 // planes: lnprior[i][s] = tab[row(i)][col], lnprob = lnl + lnprior, col = s or nbr[i][s]
 // (k-NN subsets, padded entries s >= nnb[i] get -inf like knn.py:815-817).  lnprob may alias lnl.
 __global__ void k_prior_add(PriorView pv, const double* lnl, int64_t n, int64_t L, const int64_t* nbr, const int64_t* nnb,
@@ -782,10 +801,12 @@ __global__ void k_prior_add(PriorView pv, const double* lnl, int64_t n, int64_t 
     if (k >= n * L) return;
     const int64_t i = k / L, s = k - i * L;
     double p = 0.0;
-    if (nbr) {
-        if (s < nnb[i]) { if (pv.tab) p = pv.tab[pv.row(i) * pv.ld + nbr[k]]; }
-        else p = -INFINITY;
-    } else if (pv.tab) p = pv.tab[pv.row(i) * pv.ld + s];
+    const int64_t col = nbr ? ((s < nnb[i]) ? nbr[k] : (int64_t)-1) : s;
+    if (col < 0) p = -INFINITY;
+    else if (pv.tab) {
+        const double* e = pv.tab + pv.row(i) * pv.ld + col;
+        p = pv.frac ? log_pos(prior_lerp(e[0], e[pv.ld], pv.frac[i])) : e[0];
+    }
     if (lnprior) lnprior[k] = p;
     if (lnprob) lnprob[k] = lnl[k] + p;
 }
@@ -801,19 +822,20 @@ __global__ void k_partition_masked(const uint32_t* __restrict__ bits, int64_t n,
 struct OmapGuard { fz_ctx* c; ~OmapGuard() { c->omap = nullptr; } };
 
 struct PriorBind {
-    const fz_prior* pr = nullptr;
-    int kind = 0;              // 0 none, 1 one row for all, 2 row i for object i, 3 rows[i]
-    bool tab_dev = false, rows_dev = false;
+    const fz_prior_lerp* pr = nullptr;
+    int kind = 0;              // 0 none, 1 one row for all, 2 row i for object i, 3 rows[i] (the interpolated form is always 3)
+    bool tab_dev = false, rows_dev = false, frac_dev = false;
     const double* tab = nullptr;           // device table when it is resident for the whole call
     int64_t chunk_bytes_per_obj = 0;       // staging a chunk needs per object (kind 2 from host memory)
 };
 struct PriorGuard { fz_ctx* c; ~PriorGuard() { c->prior = PriorView{}; } };
 
-static int prior_begin(fz_ctx* c, const fz_prior* pr, int64_t N, int64_t M, PriorBind& pb) {
+static int prior_begin(fz_ctx* c, const fz_prior_lerp* pr, int64_t N, int64_t M, PriorBind& pb) {
     c->prior = PriorView{};
     if (!pr || !pr->table) return 0;
     if (pr->P <= 0 || pr->P >= ((int64_t)1 << 31)) return fail(-4, "ln-prior table: P = %lld rows is out of range", (long long)pr->P);
-    pb.pr = pr; pb.tab_dev = is_device_ptr(pr->table); pb.rows_dev = is_device_ptr(pr->rows);
+    if (pr->frac && (!pr->rows || pr->P < 2)) return fail(-4, "interpolated prior: needs a row index and P >= 2 rows (P = %lld)", (long long)pr->P);
+    pb.pr = pr; pb.tab_dev = is_device_ptr(pr->table); pb.rows_dev = is_device_ptr(pr->rows); pb.frac_dev = is_device_ptr(pr->frac);
     if (pr->rows) pb.kind = 3;
     else if (pr->P == 1) pb.kind = 1;
     else if (pr->P == N) pb.kind = 2;
@@ -840,11 +862,17 @@ static int prior_chunk(fz_ctx* c, const PriorBind& pb, int64_t i0, int64_t n, in
         v.tab = pb.tab;
         if (pb.rows_dev) v.rows = pb.pr->rows + i0;
         else { FZCHK(c->d_prows.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_prows.p, pb.pr->rows + i0, (size_t)n * 8)); v.rows = c->d_prows.as<int64_t>(); }
+        if (pb.pr->frac) {
+            if (pb.frac_dev) v.frac = pb.pr->frac + i0;
+            else { FZCHK(c->d_pfrac.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_pfrac.p, pb.pr->frac + i0, (size_t)n * 8)); v.frac = c->d_pfrac.as<double>(); }
+        }
         int ef = 0;
         FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
-            hipLaunchKernelGGL(k_prior_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, n, pb.pr->P, d_flags);
+            if (v.frac) hipLaunchKernelGGL(k_prior_check_lerp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, v.frac, n, pb.pr->P, d_flags);
+            else hipLaunchKernelGGL(k_prior_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, n, pb.pr->P, d_flags);
             return 0;
         }));
+        if (ef && v.frac) return fail(-7, "interpolated prior: a row index outside [0, %lld] or a weight outside [0, 1]", (long long)pb.pr->P - 2);
         if (ef) return fail(-3, "ln-prior row index outside [0, %lld)", (long long)pb.pr->P);
     }
     c->prior = v;
@@ -861,17 +889,57 @@ static int prior_add(fz_ctx* c, const double* lnl, int64_t n, int64_t L, const i
     return 0;
 }
 
+// The (P, M) table of an interpolated prior from a (P, NZ, NT) base table: see k_prior_rows_from_grid and include/frankenz_hip.h
+extern "C" int fz_prior_rows_from_grid(fz_ctx* c, const double* base, int64_t P, int64_t NZ, int64_t NT, const int32_t* iz,
+                                       const double* g, const int32_t* t, int64_t M, double* table) {
+    if (!c || !base || !iz || !g || !t || !table) return fail(-1, "fz_prior_rows_from_grid: NULL argument");
+    if (P <= 0 || P > 65535 || NZ < 2 || NT <= 0 || M <= 0) return fail(-4, "fz_prior_rows_from_grid: P = %lld (1..65535), NZ = %lld (>= 2), NT = %lld, M = %lld", (long long)P, (long long)NZ, (long long)NT, (long long)M);
+    if (!is_device_ptr(table)) return fail(-1, "fz_prior_rows_from_grid: `table` must be device memory");
+    HIPCHK(hipSetDevice(c->device));
+    FZCHK(wait_for_producers(c, {base, iz, g, t, table}));
+    // host inputs are staged in the buffers of the fz_net_* entry points (nothing of theirs is live across calls)
+    const void* src[4] = {base, iz, g, t};
+    const size_t bytes[4] = {(size_t)P * NZ * NT * 8, (size_t)M * 4, (size_t)M * 8, (size_t)M * 4};
+    const void* dev[4];
+    for (int k = 0; k < 4; ++k) {
+        if (is_device_ptr(src[k])) { dev[k] = src[k]; continue; }
+        FZCHK(c->d_net[k].ensure(bytes[k])); FZCHK(copy_in(c, c->d_net[k].p, src[k], bytes[k])); dev[k] = c->d_net[k].p;
+    }
+    int ef = 0;
+    FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
+        hipLaunchKernelGGL(k_prior_grid_check, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)dev[1], (const double*)dev[2],
+                           (const int32_t*)dev[3], M, NZ, NT, d_flags);
+        return 0;
+    }));
+    if (ef) return fail(-7, "fz_prior_rows_from_grid: a cell outside [0, %lld], a type outside [0, %lld) or a weight outside [0, 1]", (long long)NZ - 2, (long long)NT);
+    Timer tm(c, &c->tm.ms_other, &c->tm.n_other);
+    hipLaunchKernelGGL(k_prior_rows_from_grid, dim3((unsigned)((M + 255) / 256), (unsigned)P), dim3(256), 0, c->stream, (const double*)dev[0], P, NZ, NT,
+                       (const int32_t*)dev[1], (const double*)dev[2], (const int32_t*)dev[3], M, table);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // fz_fit : BruteForce._fit (bruteforce.py:127-205)
 // ---------------------------------------------------------------------------
+// fz_prior as the interpolated form's struct with no weights: the one implementation behind both families of entry points
+static fz_prior_lerp prior_plain(const fz_prior* pr) { return fz_prior_lerp{pr->table, pr->P, pr->rows, nullptr}; }
 extern "C" int fz_fit_prior(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, const fz_prior* pr,
                             double* lnprior, double* lnlike, double* lnprob, double* chi2, int64_t* ndim, double* scale,
                             double* scale_err) {
+    fz_prior_lerp pl{};
+    if (pr) pl = prior_plain(pr);
+    return fz_fit_prior_lerp(c, x, xe, xm, N, o, pr ? &pl : nullptr, lnprior, lnlike, lnprob, chi2, ndim, scale, scale_err);
+}
+extern "C" int fz_fit_prior_lerp(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, const fz_prior_lerp* pr,
+                                 double* lnprior, double* lnlike, double* lnprob, double* chi2, int64_t* ndim, double* scale,
+                                 double* scale_err) {
     if (!c || !x || !xe || !xm || !o) return fail(-1, "fz_fit: NULL argument");
     if (!c->M) return fail(-1, "fz_fit: models have not been uploaded");
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    FZCHK(wait_for_producers(c, {x, xe, xm, pr ? pr->table : nullptr, pr ? pr->rows : nullptr}));
+    FZCHK(wait_for_producers(c, {x, xe, xm, pr ? pr->table : nullptr, pr ? pr->rows : nullptr, pr ? pr->frac : nullptr}));
     const int mode = eff_mode(c, like_mode(o));
     const int64_t M = c->M;
     PriorBind pb; PriorGuard guard{c};
@@ -916,7 +984,7 @@ extern "C" int fz_fit_prior(fz_ctx* c, double* x, double* xe, double* xm, int64_
 }
 extern "C" int fz_fit(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, double* lnlike,
                       double* chi2, int64_t* ndim, double* scale, double* scale_err) {
-    return fz_fit_prior(c, x, xe, xm, N, o, nullptr, nullptr, lnlike, nullptr, chi2, ndim, scale, scale_err);
+    return fz_fit_prior_lerp(c, x, xe, xm, N, o, nullptr, nullptr, lnlike, nullptr, chi2, ndim, scale, scale_err);
 }
 
 // ---------------------------------------------------------------------------
@@ -924,18 +992,24 @@ extern "C" int fz_fit(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, c
 // ---------------------------------------------------------------------------
 extern "C" int fz_fit_predict(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
                               const fz_kde_opts* ko, double* pdfs, double* lmap, double* levid) {
-    return fz_fit_predict_prior(c, x, xe, xm, N, o, ko, nullptr, pdfs, lmap, levid);
+    return fz_fit_predict_prior_lerp(c, x, xe, xm, N, o, ko, nullptr, pdfs, lmap, levid);
 }
 static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
-                            const fz_kde_opts* ko, const fz_prior* pr, double* pdfs, double* lmap, double* levid);
+                            const fz_kde_opts* ko, const fz_prior_lerp* pr, double* pdfs, double* lmap, double* levid);
 extern "C" int fz_fit_predict_prior(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
                                     const fz_kde_opts* ko, const fz_prior* pr, double* pdfs, double* lmap, double* levid) {
+    fz_prior_lerp pl{};
+    if (pr) pl = prior_plain(pr);
+    return fz_fit_predict_prior_lerp(c, x, xe, xm, N, o, ko, pr ? &pl : nullptr, pdfs, lmap, levid);
+}
+extern "C" int fz_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
+                                         const fz_kde_opts* ko, const fz_prior_lerp* pr, double* pdfs, double* lmap, double* levid) {
     if (!c || !x || !xe || !xm || !o || !pdfs) return fail(-1, "fz_fit_predict: NULL argument");
     if (!c->M) return fail(-1, "fz_fit_predict: models have not been uploaded");
     FZCHK(check_kde_opts(ko));
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    FZCHK(wait_for_producers(c, {x, xe, xm, pr ? pr->table : nullptr, pr ? pr->rows : nullptr}));
+    FZCHK(wait_for_producers(c, {x, xe, xm, pr ? pr->table : nullptr, pr ? pr->rows : nullptr, pr ? pr->frac : nullptr}));
     // Host objects: the whole (N, B) x 3 set goes to the device ONCE (120 MB at 1e6 x 5), is cleaned there, and comes back only if the
     // clean changed anything -- staged chunk by chunk, every chunk's six small synchronous copies waited for the previous chunk's kernel
     // and left the GPU idle meanwhile (~5 ms per chunk)
@@ -1017,7 +1091,7 @@ static int fitpredict_special_forms(fz_ctx* c, int mode, int var, int dim_prior,
     return 1;
 }
 static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o,
-                            const fz_kde_opts* ko, const fz_prior* pr, double* pdfs, double* lmap, double* levid) {
+                            const fz_kde_opts* ko, const fz_prior_lerp* pr, double* pdfs, double* lmap, double* levid) {
     const int mode = eff_mode(c, like_mode(o));
     const int64_t M = c->M, G = c->G;
     if (c->label_mode == 0) return fail(-1, "fz_fit_predict: labels have not been uploaded");

@@ -44,13 +44,21 @@ struct ObjView {
 // Additive ln-prior (extension; SURVEY 8f-1 -- the lnprior a custom lprob_func returns,
 // bruteforce.py:193-194): row-major table of ln-prior rows over the M models and the row
 // each object of the chunk reads.  lnprob[i][j] = lnlike[i][j] + tab[row(i) * ld + j].
+// Interpolated form (frac != nullptr; docs/bpz_prior.md): the table holds prior VALUES and object i reads rows row(i) and
+// row(i) + 1 with the weights 1 - frac[i] and frac[i]:  lnprior[i][j] = ln((1 - f) tab[r][j] + f tab[r + 1][j]).
 struct PriorView {
     const double* tab;     // nullptr: no prior
     const int64_t* rows;   // [n] row per object (validated against P on the device), or nullptr
+    const double* frac;    // [n] weight of row rows[i] + 1 (validated to [0, 1] on the device), or nullptr: a table of ln values
     int64_t ident;         // rows == nullptr: 1 -> object i reads row i, 0 -> every object reads row 0
     int64_t ld;            // row length (= M)
     __device__ __forceinline__ int64_t row(int64_t i) const { return rows ? rows[i] : (ident ? i : 0); }
 };
+// The interpolated prior value of one pair, a and b being the entries of the two rows.  Two products and a sum of non-negative
+// terms, as the reference's interpolator sums its weighted corners: no cancellation for any f in [0, 1] (1 - f is exact for
+// f >= 1/2 and correctly rounded below), so the value is within 3 roundings of the exact one and is zero exactly when every
+// corner with a non-zero weight is zero.  (The one-product form fma(f, b - a, a) loses b altogether where b << a and f -> 1.)
+__device__ __forceinline__ double prior_lerp(double a, double b, double f) { return fma(f, b, (1.0 - f) * a); }
 struct LikeParams {
     int dim_prior;
     const double* lgtab;   // [BT+1] gammaln(a)+a*ln2, a=n/2 (modes 0,1) or (n-1)/2 (mode 2)

@@ -18,9 +18,9 @@ static_assert(false FZ_BT_LIST(FZ_BT_OR), "FZ_BT is not a band count of FZ_BT_LI
 // counts always carry mask bits.
 #define FZ_EXACT_BT (FZ_BT >= 4 && FZ_BT <= 8)
 
-// The ln-weight source of likelihood MODE in arithmetic variant VAR (PRI: with the chunk's additive ln-prior) on the models and the
-// prepared chunk of c: the one place a PhotSrc is filled in.
-template <int MODE, int VAR, bool PRI = false>
+// The ln-weight source of likelihood MODE in arithmetic variant VAR (PRI 1: with the chunk's additive ln-prior, 2: with its
+// interpolated prior) on the models and the prepared chunk of c: the one place a PhotSrc is filled in.
+template <int MODE, int VAR, int PRI = 0>
 static PhotSrc<FZ_BT, MODE, VAR, PRI> phot_src(fz_ctx* c, int dim_prior) {
     PhotSrc<FZ_BT, MODE, VAR, PRI> ph;
     ph.mv = model_view(c); ph.ov = obj_view(c); ph.lp = like_params(c, MODE, dim_prior);
@@ -137,7 +137,8 @@ static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t
     return with_mode_var(mode, var, [&](auto MODE, auto VAR) -> int {
         constexpr int MD = decltype(MODE)::value, VR = decltype(VAR)::value;
 #if !defined(FZ_DEV_FAST)
-        if (c->prior.tab) return fz_launch_fitpredict(c, phot_src<MD, VR, true>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
+        if (c->prior.tab && c->prior.frac) return fz_launch_fitpredict(c, phot_src<MD, VR, 2>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
+        if (c->prior.tab) return fz_launch_fitpredict(c, phot_src<MD, VR, 1>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
 #endif
         return fz_launch_fitpredict(c, phot_src<MD, VR>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
     });

@@ -35,7 +35,8 @@ struct PlaneSrc {
         return valid ? o.row[j] : -INFINITY;
     }
 };
-template <int BT, int MODE, int VAR, bool PRI = false>
+// PRI: 0 no prior, 1 a table of ln-prior rows, 2 a table of prior values read by interpolation (PriorView::frac)
+template <int BT, int MODE, int VAR, int PRI = 0>
 struct PhotSrc : Phot<BT, MODE, VAR> {
     using P = Phot<BT, MODE, VAR>;
     // With the dimensionality prior and no masks the likelihood is chi2^(WPOW/2) e^(-chi2/2)/C
@@ -43,7 +44,7 @@ struct PhotSrc : Phot<BT, MODE, VAR> {
     // the weight can be formed with a square root instead of a logarithm (k_fused, WM).
     // An additive ln-prior (PRI) keeps to the ln-space body, which tracks nan / +-inf rows.
     static constexpr int WPOW = (VAR == VAR_FAST && !PRI) ? (MODE == 2 ? BT - 3 : BT - 2) : 0;
-    static constexpr bool HAS_PRIOR = PRI;
+    static constexpr bool HAS_PRIOR = PRI != 0;
     static constexpr int NB = BT;
     static constexpr int LMODE = MODE;
     // mask-free tame data cannot produce a nan ln-like (chi2 is finite and >= 0, the exponent of the
@@ -53,20 +54,31 @@ struct PhotSrc : Phot<BT, MODE, VAR> {
     static constexpr bool PREF_2x16 = (BT <= 6) && ((MODE == 1) || (MODE == 2) || (MODE == 0 && VAR != VAR_FAST));   // r1_v7 sweep: masked mode B 150 vs 161 ms at (4,8)
     static constexpr bool PREF_2x8 = false;   // r1_v7 sweep: 7 / 8-band unmasked mode A now runs best at (4,8): 97 vs 105 ms, 103 vs 109 ms (was (2,8) before the lean instantiation)
     PriorView pv;                                 // read only when PRI
-    struct OR : P::OR { const double* prow; };    // + the object's ln-prior row
+    // + the object's ln-prior row; interpolated form (PRI == 2): the lower of its two rows and the weight of the upper
+    struct OR : P::OR { const double* prow; double pf; };
     __device__ __forceinline__ void load_obj(int64_t i, OR& o) const {
         P::load_obj(i, o);
         if (PRI) o.prow = pv.tab + pv.row(i) * pv.ld;
+        if (PRI == 2) o.pf = pv.frac[i];
     }
     // the row index (< 2^31, checked on the host) rides in the spare high word of the
-    // parked object row's mask slot
+    // parked object row's mask slot, the interpolation weight in a slot of its own (rows stay 16-byte multiples)
+    static constexpr int OBJ_DOUBLES = P::OBJ_DOUBLES + (PRI == 2 ? 2 : 0);
     __device__ __forceinline__ void park_obj(int64_t i, double* dst, int lane) const {
         P::park_obj(i, dst, lane);
         if (PRI && lane == BT) dst[2 * BT + 1] = __hiloint2double((int)pv.row(i), P::MASKED ? (int)P::ov.bits[i] : -1);
+        if (PRI == 2 && lane == BT) dst[2 * BT + 2] = pv.frac[i];
     }
     __device__ __forceinline__ void load_obj_lds(const double* p, OR& o) const {
         P::load_obj_lds(p, o);
         if (PRI) o.prow = pv.tab + (int64_t)__double2hiint(p[2 * BT + 1]) * pv.ld;
+        if (PRI == 2) o.pf = p[2 * BT + 2];
+    }
+    // ln-prior of the pair (o, model j): the table entry, or the log of the two rows' interpolated value
+    __device__ __forceinline__ double lnprior(const OR& o, int64_t j) const {
+        const double a = o.prow[j];
+        if (PRI == 2) return log_pos(prior_lerp(a, o.prow[j + pv.ld], o.pf), P::tb);
+        return a;
     }
     __device__ __forceinline__ double chi2_of(const typename P::OR& o, const typename P::MR& m) const {
         return P::template eval<1>(o, m).chi2;          // the unused ln-like tail is dead code
@@ -80,14 +92,14 @@ struct PhotSrc : Phot<BT, MODE, VAR> {
     }
     __device__ __forceinline__ double lnl(const OR& o, const typename P::MR& m, int64_t j, bool valid) const {
         double l = P::eval(o, m).lnl;             // pad lanes hold benign data; no divergent branch
-        if (PRI) l += valid ? o.prow[j] : 0.0;
+        if (PRI) l += valid ? lnprior(o, j) : 0.0;
         return valid ? l : -INFINITY;
     }
     // j / inb: the lane's model and whether it is a real one (only the prior read needs them)
     template <int DPT>
     __device__ __forceinline__ double lnl_t(const OR& o, const typename P::MR& m, int j, bool inb) const {
         double l = P::template eval<DPT>(o, m).lnl;
-        if (PRI) l += inb ? o.prow[j] : 0.0;
+        if (PRI) l += inb ? lnprior(o, j) : 0.0;
         return l;
     }
 

@@ -236,6 +236,16 @@ extern "C" int fz_knn_fit_predict_prior(fz_ctx* c, double* x, double* xe, double
                                         int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
                                         int64_t* ndim, double* scale, double* scale_err, double* pdfs, double* lmap,
                                         double* levid) {
+    fz_prior_lerp pl{};
+    if (pr) pl = prior_plain(pr);
+    return fz_knn_fit_predict_prior_lerp(c, x, xe, xm, N, idx, W, o, ko, pr ? &pl : nullptr, neighbors, nnbr, lnprior, lnlike, lnprob, chi2, ndim,
+                                         scale, scale_err, pdfs, lmap, levid);
+}
+extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const int64_t* idx, int64_t W,
+                                             const fz_like_opts* o, const fz_kde_opts* ko, const fz_prior_lerp* pr, int64_t* neighbors,
+                                             int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
+                                             int64_t* ndim, double* scale, double* scale_err, double* pdfs, double* lmap,
+                                             double* levid) {
     if (!c || !x || !xe || !xm || !idx || !o) return fail(-1, "fz_knn_fit_predict: NULL argument");
     if (!c->M) return fail(-1, "fz_knn_fit_predict: models have not been uploaded");
     if (W <= 0 || W > FZ_KNN_WMAX) return fail(-5, "fz_knn_fit_predict: K*k = %lld unsupported (max %d)", (long long)W, FZ_KNN_WMAX);
@@ -346,8 +356,8 @@ extern "C" int fz_knn_fit_predict(fz_ctx* c, double* x, double* xe, double* xm, 
                                   const fz_like_opts* o, const fz_kde_opts* ko, int64_t* neighbors, int64_t* nnbr,
                                   double* lnlike, double* chi2, int64_t* ndim, double* scale, double* scale_err,
                                   double* pdfs, double* lmap, double* levid) {
-    return fz_knn_fit_predict_prior(c, x, xe, xm, N, idx, W, o, ko, nullptr, neighbors, nnbr, nullptr, lnlike, nullptr, chi2, ndim,
-                                    scale, scale_err, pdfs, lmap, levid);
+    return fz_knn_fit_predict_prior_lerp(c, x, xe, xm, N, idx, W, o, ko, nullptr, neighbors, nnbr, nullptr, lnlike, nullptr, chi2, ndim,
+                                         scale, scale_err, pdfs, lmap, levid);
 }
 
 // knn.py:826-874 in one call: the K searches AND the subset likelihood / PDFs, with the (N, K*k) neighbour table never leaving the
@@ -359,6 +369,16 @@ extern "C" int fz_knn_search_fit_predict_prior(fz_ctx* c, const double* q, doubl
                                                const fz_prior* pr, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike,
                                                double* lnprob, double* chi2, int64_t* ndim, double* scale, double* scale_err,
                                                double* pdfs, double* lmap, double* levid) {
+    fz_prior_lerp pl{};
+    if (pr) pl = prior_plain(pr);
+    return fz_knn_search_fit_predict_prior_lerp(c, q, x, xe, xm, N, k, lp_norm, dub, o, ko, pr ? &pl : nullptr, neighbors, nnbr, lnprior, lnlike,
+                                                lnprob, chi2, ndim, scale, scale_err, pdfs, lmap, levid);
+}
+extern "C" int fz_knn_search_fit_predict_prior_lerp(fz_ctx* c, const double* q, double* x, double* xe, double* xm, int64_t N, int32_t k,
+                                                    double lp_norm, double dub, const fz_like_opts* o, const fz_kde_opts* ko,
+                                                    const fz_prior_lerp* pr, int64_t* neighbors, int64_t* nnbr, double* lnprior,
+                                                    double* lnlike, double* lnprob, double* chi2, int64_t* ndim, double* scale,
+                                                    double* scale_err, double* pdfs, double* lmap, double* levid) {
     if (!c || !q || !x || !xe || !xm || !o) return fail(-1, "fz_knn_search_fit_predict: NULL argument");
     if (!c->knn_K) return fail(-1, "fz_knn_search_fit_predict: feature sets have not been uploaded");
     if (k <= 0) return fail(-5, "fz_knn_search_fit_predict: k=%d unsupported", k);
@@ -381,9 +401,10 @@ extern "C" int fz_knn_search_fit_predict_prior(fz_ctx* c, const double* q, doubl
         const double* dq;
         if (qdev) dq = q + i0 * F; else { FZCHK(c->d_q.ensure((size_t)n * F * 8)); FZCHK(copy_in(c, c->d_q.p, q + i0 * F, (size_t)n * F * 8)); dq = c->d_q.as<double>(); }
         FZCHK(run_knnquery(c, dq, n, k, b2, c->d_idxs.as<int64_t>(), pnorm));
-        fz_prior pc; const fz_prior* prc = nullptr;
+        fz_prior_lerp pc; const fz_prior_lerp* prc = nullptr;
         if (pr && pr->table) {
             pc = *pr; prc = &pc;
+            if (pr->frac) pc.frac = pr->frac + i0;
             if (pr->rows) pc.rows = pr->rows + i0;
             else if (pr->P != 1) {
                 if (pr->P != N) return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
@@ -391,9 +412,9 @@ extern "C" int fz_knn_search_fit_predict_prior(fz_ctx* c, const double* q, doubl
             }
         }
         auto at = [&](auto* p, int64_t per) { return p ? p + i0 * per : p; };
-        FZCHK(fz_knn_fit_predict_prior(c, x + i0 * B, xe + i0 * B, xm + i0 * B, n, c->d_idxs.as<int64_t>(), W, o, ko, prc, at(neighbors, W), at(nnbr, 1),
-                                       at(lnprior, W), at(lnlike, W), at(lnprob, W), at(chi2, W), at(ndim, W), at(scale, W), at(scale_err, W),
-                                       at(pdfs, G), at(lmap, 1), at(levid, 1)));
+        FZCHK(fz_knn_fit_predict_prior_lerp(c, x + i0 * B, xe + i0 * B, xm + i0 * B, n, c->d_idxs.as<int64_t>(), W, o, ko, prc, at(neighbors, W),
+                                            at(nnbr, 1), at(lnprior, W), at(lnlike, W), at(lnprob, W), at(chi2, W), at(ndim, W), at(scale, W),
+                                            at(scale_err, W), at(pdfs, G), at(lmap, 1), at(levid, 1)));
     }
     return 0;
 }

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import KdeOpts, LikeOpts, Prior, Timing, check, ptr
+from ._lib import KdeOpts, LikeOpts, Prior, PriorLerp, Timing, check, ptr
 
 # the reference's logprob keywords + one extension: exact_evidence=True sums every weight of the fused path's
 # ln-evidence in fp64 (default: the weights below wt_thresh of the best are summed in fp32, ~1e-9 on levid)
@@ -261,25 +261,37 @@ class Engine(object):
 
     @staticmethod
     def _prior_struct(prior):
-        """(table, P, rows) -> fz_prior*, or NULL.  The arrays must outlive the call."""
+        """(table, P, rows) -> ("", fz_prior*) or ("", NULL); (table, P, rows, frac) -> ("_lerp", fz_prior_lerp*): the suffix of
+        the entry point that takes the struct.  The arrays must outlive the call."""
         if prior is None:
-            return None
+            return "", None
+        if len(prior) == 4:
+            table, P, rows, frac = prior
+            return "_lerp", C.byref(PriorLerp(ptr(table), int(P), ptr(rows), ptr(frac)))
         table, P, rows = prior
-        return C.byref(Prior(ptr(table), int(P), ptr(rows)))
+        return "", C.byref(Prior(ptr(table), int(P), ptr(rows)))
 
     def fit_prior(self, x, xe, xm, opts, prior, lnprior=None, lnlike=None, lnprob=None, chi2=None,
                   ndim=None, scale=None, scale_err=None, n=None):
-        """fz_fit_prior: ``prior`` is ``(table (P,M), P, rows (n,) or None)`` or None."""
+        """fz_fit_prior: ``prior`` is ``(table (P,M), P, rows (n,) or None)`` or None; with a fourth entry ``frac (n,)`` it is
+        the interpolated form (fz_fit_prior_lerp)."""
         n = len(x) if n is None else n
-        check(self.lib.fz_fit_prior(self.h, ptr(x), ptr(xe), ptr(xm), n, C.byref(opts),
-                                    self._prior_struct(prior), ptr(lnprior), ptr(lnlike), ptr(lnprob),
-                                    ptr(chi2), ptr(ndim), ptr(scale), ptr(scale_err)))
+        sfx, ps = self._prior_struct(prior)
+        check(getattr(self.lib, "fz_fit_prior" + sfx)(self.h, ptr(x), ptr(xe), ptr(xm), n, C.byref(opts),
+                                                      ps, ptr(lnprior), ptr(lnlike), ptr(lnprob),
+                                                      ptr(chi2), ptr(ndim), ptr(scale), ptr(scale_err)))
 
     def fit_predict_prior(self, x, xe, xm, opts, kopts, prior, pdfs, lmap=None, levid=None, n=None):
         n = len(x) if n is None else n
-        check(self.lib.fz_fit_predict_prior(self.h, ptr(x), ptr(xe), ptr(xm), n, C.byref(opts),
-                                            C.byref(kopts), self._prior_struct(prior), ptr(pdfs),
-                                            ptr(lmap), ptr(levid)))
+        sfx, ps = self._prior_struct(prior)
+        check(getattr(self.lib, "fz_fit_predict_prior" + sfx)(self.h, ptr(x), ptr(xe), ptr(xm), n, C.byref(opts),
+                                                              C.byref(kopts), ps, ptr(pdfs), ptr(lmap), ptr(levid)))
+
+    def prior_rows_from_grid(self, base, iz, g, t, table):
+        """fz_prior_rows_from_grid: ``base`` (P, NZ, NT) float64, ``iz`` / ``t`` (M,) int32, ``g`` (M,) float64 -> the device
+        ``table`` (P, M)."""
+        P, NZ, NT = base.shape
+        check(self.lib.fz_prior_rows_from_grid(self.h, ptr(base), P, NZ, NT, ptr(iz), ptr(g), ptr(t), len(iz), ptr(table)))
 
     def predict_logwt(self, logwt, kopts, pdfs, lmap=None, levid=None, is_log=True, n=None):
         n = len(logwt) if n is None else n
@@ -316,9 +328,10 @@ class Engine(object):
                               lnprior=None, lnlike=None, lnprob=None, chi2=None, ndim=None, scale=None,
                               scale_err=None, pdfs=None, lmap=None, levid=None, n=None):
         n = len(x) if n is None else n
-        check(self.lib.fz_knn_fit_predict_prior(
+        sfx, ps = self._prior_struct(prior)
+        check(getattr(self.lib, "fz_knn_fit_predict_prior" + sfx)(
             self.h, ptr(x), ptr(xe), ptr(xm), n, ptr(idx), int(W), C.byref(opts),
-            C.byref(kopts) if kopts is not None else None, self._prior_struct(prior), ptr(neighbors),
+            C.byref(kopts) if kopts is not None else None, ps, ptr(neighbors),
             ptr(nnbr), ptr(lnprior), ptr(lnlike), ptr(lnprob), ptr(chi2), ptr(ndim), ptr(scale),
             ptr(scale_err), ptr(pdfs), ptr(lmap), ptr(levid)))
 
@@ -433,9 +446,10 @@ class Engine(object):
         """fz_knn_search_fit_predict_prior: the K searches and the subset likelihood / PDFs in one call, the neighbour
         table staying on the device"""
         n = len(x) if n is None else n
-        check(self.lib.fz_knn_search_fit_predict_prior(
+        sfx, ps = self._prior_struct(prior)
+        check(getattr(self.lib, "fz_knn_search_fit_predict_prior" + sfx)(
             self.h, ptr(q), ptr(x), ptr(xe), ptr(xm), n, int(k), float(lp_norm), float(distance_upper_bound),
-            C.byref(opts), C.byref(kopts) if kopts is not None else None, self._prior_struct(prior), ptr(neighbors),
+            C.byref(opts), C.byref(kopts) if kopts is not None else None, ps, ptr(neighbors),
             ptr(nnbr), ptr(lnprior), ptr(lnlike), ptr(lnprob), ptr(chi2), ptr(ndim), ptr(scale), ptr(scale_err),
             ptr(pdfs), ptr(lmap), ptr(levid)))
 
@@ -505,6 +519,15 @@ class DeviceArray(object):
 
     def __len__(self):
         return self.shape[0]
+
+    def dim(self):
+        return len(self.shape)
+
+    def is_contiguous(self):
+        return True
+
+    def element_size(self):
+        return self.dtype.itemsize
 
     def numpy(self):
         out = np.empty(self.shape, dtype=self.dtype)

@@ -16,7 +16,7 @@ import numpy as np
 
 from .engine import HostObjects, get_engine, kde_opts, like_opts
 
-__all__ = ["loglike", "logprob", "logprob_prior", "gaussian", "gauss_kde", "gauss_kde_dict",
+__all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
            "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample"]
 
 
@@ -108,29 +108,97 @@ class logprob_prior(object):
     def __call__(self, data, data_err, data_mask, models, models_err, models_mask, row=0,
                  free_scale=False, ignore_model_err=False, dim_prior=True, ltol=1e-4,
                  return_scale=False, device=None):
-        eng = get_engine(device)
-        eng.upload_models(models, models_err, models_mask)
-        if eng.M != self.M:
-            raise ValueError("ln-prior rows hold %d models, the model set %d" % (self.M, eng.M))
-        obj = HostObjects(np.atleast_2d(data), np.atleast_2d(data_err), np.atleast_2d(data_mask))
-        M = eng.M
-        lnp, lnl, lpr, chi2 = (np.empty((1, M)) for _ in range(4))
-        ndim = np.empty((1, M), dtype=np.int64)
-        sc = se = None
-        if free_scale and return_scale:
-            sc, se = np.empty((1, M)), np.empty((1, M))
-        opts = like_opts(dict(free_scale=free_scale, ignore_model_err=ignore_model_err,
-                              dim_prior=dim_prior, ltol=ltol))
         rows = np.array([row], dtype=np.int64)
-        eng.fit_prior(obj.x, obj.xe, obj.xm, opts, (self.table, self.P, rows), lnp, lnl, lpr, chi2,
-                      ndim, sc, se)
-        for dst, buf in ((data, obj.x), (data_err, obj.xe), (data_mask, obj.xm)):
-            if isinstance(dst, np.ndarray) and not np.shares_memory(dst, buf):
-                dst[...] = buf.reshape(dst.shape)
-        out = (lnp[0], lnl[0], lpr[0], ndim[0].astype(_ndim_dtype(data_mask, models_mask)), chi2[0])
-        if free_scale and return_scale:
-            out = out + (sc[0], se[0])
-        return out
+        return _prior_one_object(self.M, (self.table, self.P, rows), data, data_err, data_mask, models, models_err,
+                                 models_mask, free_scale, ignore_model_err, dim_prior, ltol, return_scale, device)
+
+
+def _prior_one_object(Mtab, prior, data, data_err, data_mask, models, models_err, models_mask, free_scale,
+                      ignore_model_err, dim_prior, ltol, return_scale, device):
+    """one object through ``fz_fit_prior`` / ``fz_fit_prior_lerp`` with the reference's ``lprob_func`` return tuple; ``prior``
+    is the engine's prior tuple for that object"""
+    eng = get_engine(device)
+    eng.upload_models(models, models_err, models_mask)
+    if eng.M != Mtab:
+        raise ValueError("ln-prior rows hold %d models, the model set %d" % (Mtab, eng.M))
+    obj = HostObjects(np.atleast_2d(data), np.atleast_2d(data_err), np.atleast_2d(data_mask))
+    M = eng.M
+    lnp, lnl, lpr, chi2 = (np.empty((1, M)) for _ in range(4))
+    ndim = np.empty((1, M), dtype=np.int64)
+    sc = se = None
+    if free_scale and return_scale:
+        sc, se = np.empty((1, M)), np.empty((1, M))
+    opts = like_opts(dict(free_scale=free_scale, ignore_model_err=ignore_model_err,
+                          dim_prior=dim_prior, ltol=ltol))
+    eng.fit_prior(obj.x, obj.xe, obj.xm, opts, prior, lnp, lnl, lpr, chi2, ndim, sc, se)
+    for dst, buf in ((data, obj.x), (data_err, obj.xe), (data_mask, obj.xm)):
+        if isinstance(dst, np.ndarray) and not np.shares_memory(dst, buf):
+            dst[...] = buf.reshape(dst.shape)
+    out = (lnp[0], lnl[0], lpr[0], ndim[0].astype(_ndim_dtype(data_mask, models_mask)), chi2[0])
+    if free_scale and return_scale:
+        out = out + (sc[0], se[0])
+    return out
+
+
+def lerp_cells(grid, coord):
+    """Cell and fraction of every ``coord`` on the strictly ascending nodes ``grid`` (P >= 2): ``coord`` is clipped to the grid,
+    ``r = clip(searchsorted(grid, coord, 'right') - 1, 0, P - 2)`` and ``f = (coord - grid[r]) / (grid[r + 1] - grid[r])``, so
+    that the top node is ``(P - 2, 1.0)`` and row ``P`` is never read.  ``nan`` raises ``ValueError``."""
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    coord = np.atleast_1d(np.asarray(coord, dtype=np.float64))
+    if grid.ndim != 1 or len(grid) < 2:
+        raise ValueError("an interpolated prior needs a 1-D `grid` of at least 2 nodes")
+    if not np.all(np.diff(grid) > 0):
+        raise ValueError("`grid` must be strictly ascending (and free of nan)")
+    if coord.ndim != 1:
+        raise ValueError("`coord` must be one number per object")
+    if np.isnan(coord).any():
+        raise ValueError("`coord` holds nan: the interpolated prior is undefined there")
+    c = np.clip(coord, grid[0], grid[-1])
+    r = np.clip(np.searchsorted(grid, c, side='right') - 1, 0, len(grid) - 2).astype(np.int64)
+    f = (c - grid[r]) / (grid[r + 1] - grid[r])
+    return r, np.ascontiguousarray(f, dtype=np.float64)
+
+
+class logprob_prior_lerp(object):
+    """``lprob_func`` with a prior that is LINEAR along one per-object coordinate (extension; the BPZ prior P(z, t | m) of the
+    reference's priors.py along the magnitude, ``priors.logprob_bpz``):
+
+        lnprior[i][j] = ln((1 - f_i) table[r_i][j] + f_i table[r_i + 1][j])
+
+    ``table`` is ``(P, Nmodel)`` float64 prior VALUES (not logarithms; NumPy array or a device tensor exposing
+    ``data_ptr()``) on the ``P >= 2`` strictly ascending nodes ``grid``, ``coord`` the ``(Ndata,)`` coordinate of every object
+    (clipped to the grid; ``nan`` raises ``ValueError``) and ``(r_i, f_i)`` its cell and fraction (``lerp_cells``).  A zero
+    value gives ``-inf``, a negative or nan value ``nan``, like ``np.log``.
+
+    Used like ``logprob_prior``; the one-object call takes ``index=``, the object's position in ``coord``."""
+
+    def __init__(self, table, grid, coord):
+        if isinstance(table, np.ndarray) or not hasattr(table, "data_ptr"):
+            table = np.ascontiguousarray(table, dtype=np.float64)
+            if table.ndim != 2:
+                raise ValueError("the prior table must be 2-D (P, Nmodel)")
+        elif table.dim() != 2 or not table.is_contiguous() or table.element_size() != 8:
+            raise ValueError("a device prior table must be a contiguous 2-D float64 tensor")
+        self.table = table
+        self.P, self.M = int(table.shape[0]), int(table.shape[1])
+        self.grid = np.ascontiguousarray(grid, dtype=np.float64)
+        if self.grid.shape != (self.P,):
+            raise ValueError("`grid` has shape %s for a table of %d rows" % (self.grid.shape, self.P))
+        self.rows, self.frac = lerp_cells(self.grid, coord)
+
+    def chunk(self, lo, hi, Ndata):
+        """the ``(table, P, rows, frac)`` tuple of objects [lo, hi) out of Ndata"""
+        if len(self.rows) != Ndata:
+            raise ValueError("the prior's `coord` has %d entries for %d objects" % (len(self.rows), Ndata))
+        return self.table, self.P, self.rows[lo:hi], self.frac[lo:hi]
+
+    def __call__(self, data, data_err, data_mask, models, models_err, models_mask, index=0,
+                 free_scale=False, ignore_model_err=False, dim_prior=True, ltol=1e-4,
+                 return_scale=False, device=None):
+        prior = (self.table, self.P, self.rows[index:index + 1].copy(), self.frac[index:index + 1].copy())
+        return _prior_one_object(self.M, prior, data, data_err, data_mask, models, models_err, models_mask, free_scale,
+                                 ignore_model_err, dim_prior, ltol, return_scale, device)
 
 
 def gaussian(mu, std, x):

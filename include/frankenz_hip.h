@@ -192,6 +192,33 @@ int  fz_fit_predict_prior(fz_ctx* ctx, double* x, double* xe, double* xm, int64_
                           const fz_like_opts* opts, const fz_kde_opts* kde,
                           const fz_prior* prior, double* pdfs, double* lmap, double* levid);
 
+/* ---- interpolated prior (extension; docs/bpz_prior.md) ----
+ * A prior that is linear along one per-object coordinate (the BPZ prior P(z, t | m) of the reference's priors.py along the
+ * magnitude m): table holds prior VALUES, not logarithms, on P nodes of that coordinate, and object i reads the two rows
+ * rows[i] and rows[i] + 1 with the weights 1 - frac[i] and frac[i]:
+ *     lnprior[i][j] = ln((1 - frac[i]) * table[rows[i]][j] + frac[i] * table[rows[i] + 1][j]).
+ * A zero value gives -inf, a negative or nan value nan.  rows outside [0, P - 2] or frac outside [0, 1] are refused (-7) before
+ * any kernel reads the table.  frac == NULL makes every entry point below the fz_prior call of the same name (a table of ln rows). */
+typedef struct fz_prior_lerp {
+    const double*  table;  /* (P,M) float64 row-major, host or device          */
+    int64_t        P;      /* 2 <= P < 2^31                                     */
+    const int64_t* rows;   /* (N) int64 in [0,P-2], host or device              */
+    const double*  frac;   /* (N) float64 in [0,1], host or device              */
+} fz_prior_lerp;
+int  fz_fit_prior_lerp(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N,
+                       const fz_like_opts* opts, const fz_prior_lerp* prior, double* lnprior,
+                       double* lnlike, double* lnprob, double* chi2, int64_t* ndim,
+                       double* scale, double* scale_err);
+int  fz_fit_predict_prior_lerp(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N,
+                               const fz_like_opts* opts, const fz_kde_opts* kde,
+                               const fz_prior_lerp* prior, double* pdfs, double* lmap, double* levid);
+/* The table of such a prior for M models from a base table on a regular (coordinate, z, type) grid: base (P, NZ, NT) float64,
+ * model j sits in z cell iz[j] in [0, NZ - 2] with the weight g[j] in [0, 1] of node iz[j] + 1 and has type t[j] in [0, NT):
+ *     table[r][j] = (1 - g[j]) * base[r][iz[j]][t[j]] + g[j] * base[r][iz[j] + 1][t[j]].
+ * base, iz, g, t: host or device; table (P, M): device memory.  Cells, types or weights out of range are refused (-7). */
+int  fz_prior_rows_from_grid(fz_ctx* ctx, const double* base, int64_t P, int64_t NZ, int64_t NT, const int32_t* iz,
+                             const double* g, const int32_t* t, int64_t M, double* table);
+
 /* BruteForce._predict (bruteforce.py:303-372): rows of logwt (N,M) -> PDFs.
  * is_log=0 treats the rows as linear weights y_wt and skips the softmax
  * (gauss_kde / gauss_kde_dict called directly, pdf.py:444, 529). */
@@ -234,6 +261,19 @@ int  fz_knn_search_fit_predict_prior(fz_ctx* ctx, const double* q, double* x, do
                                      int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike,
                                      double* lnprob, double* chi2, int64_t* ndim, double* scale,
                                      double* scale_err, double* pdfs, double* lmap, double* levid);
+/* the two calls above with an interpolated prior (fz_prior_lerp) */
+int  fz_knn_fit_predict_prior_lerp(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N,
+                                   const int64_t* idx, int64_t W, const fz_like_opts* opts,
+                                   const fz_kde_opts* kde, const fz_prior_lerp* prior, int64_t* neighbors,
+                                   int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob,
+                                   double* chi2, int64_t* ndim, double* scale, double* scale_err,
+                                   double* pdfs, double* lmap, double* levid);
+int  fz_knn_search_fit_predict_prior_lerp(fz_ctx* ctx, const double* q, double* x, double* xe, double* xm, int64_t N,
+                                          int32_t k, double lp_norm, double distance_upper_bound,
+                                          const fz_like_opts* opts, const fz_kde_opts* kde, const fz_prior_lerp* prior,
+                                          int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike,
+                                          double* lnprob, double* chi2, int64_t* ndim, double* scale,
+                                          double* scale_err, double* pdfs, double* lmap, double* levid);
 
 /* NearestNeighbors._predict (knn.py:488-558): PDFs from stored (N,W) ln-weights,
  * the stored neighbour table (N,W) and counts (N). */
