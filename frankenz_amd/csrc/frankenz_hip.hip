@@ -1245,6 +1245,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_knn_host.inc"
 #include "fz_summary_host.inc"
 #include "fz_net_host.inc"
+#include "fz_train_host.inc"
 #include "fz_som_host.inc"
 #include "fz_gng_host.inc"
 #include "fz_nzmc_host.inc"

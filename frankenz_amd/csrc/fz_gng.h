@@ -1,6 +1,6 @@
 // Training of a growing neural gas (GrowingNeuralGas._train_network, networks.py:2037-2260): ONE persistent workgroup per network
 // runs the sequential step loop itself, batch ends included.  A step draws one (cleaned) model row, takes its ln-probability against
-// every live node (noiseless, unmasked models: the arithmetic of fz_som.h), finds the best and the second-best node, moves the best
+// every live node (noiseless, unmasked models: train_lnl of fz_train.h), finds the best and the second-best node, moves the best
 // node and its graph neighbours towards the row, resets or creates the edge between the two and ages the best node's edges.  Every
 // nbatch steps the edges that reached max_age are removed, nodes left without edges are dropped (the slots are compacted, so slot
 // order is always the reference's node order) and a node is inserted next to the one with the largest accumulated error.
@@ -13,13 +13,10 @@
 //     rewrites one into the other).  Edge ids are handed out in creation order and never reused; the age of an edge is age[id].
 // docs/gng.md.
 #pragma once
-#include "fz_device.h"
-#include "fz_som.h"
+#include "fz_train.h"
 
 namespace fz {
 
-#define GNG_CHUNK 32        // steps whose rows are staged into LDS at once
-#define GNG_NT 1024         // threads of the workgroup (at most)
 #define GNG_NCNT 16         // counters at the head of the integer state
 enum { GNG_NN = 0, GNG_NP, GNG_EC, GNG_STATUS, GNG_STEP, GNG_AL0, GNG_AL1, GNG_CUR, GNG_REM };
 enum { GNG_OK = 0, GNG_E_DEGREE = 1, GNG_E_PRUNE = 2, GNG_E_NODES = 3, GNG_E_EDGES = 4 };
@@ -28,7 +25,7 @@ struct GngArgs {
     const double* x;        // (M, B) cleaned model values
     const double* xe;       // (M, B) cleaned model errors
     const double* xm;       // (M, B) cleaned mask (0/1)
-    const double* rowk;     // (M, 4) k_som_rowk
+    const double* rowk;     // (M, 4) k_train_rowk
     const int64_t* draws;   // (T) row drawn at each step
     double* fstate;         // pos[cap*B] fit[cap*B] err[cap] alias_rows[2*B]
     int32_t* istate;        // cnt[GNG_NCNT] deg[cap] aux[cap] adj[2][cap*md](nbr, edge) prune[pcap](u, v, edge) age[ecap]
@@ -44,9 +41,9 @@ struct GngArgs {
     int free_scale, dim_prior, modec, track_scale;
 };
 
-// per-step record staged in LDS: x[B] tv[B] m[B] am1 G1 G2 K alias
-__host__ __device__ constexpr int gng_rec_width(int B) { return 3 * B + 5; }
-__host__ __device__ constexpr int gng_fixed_lds_doubles(int B) { return GNG_CHUNK * gng_rec_width(B) + 16 * 3 + 16 + 8 + 8; }
+// per-step record staged in LDS: the head (fz_train.h), then alias
+__host__ __device__ constexpr int gng_rec_width(int B) { return train_rec_head(B) + 1; }
+__host__ __device__ constexpr int gng_fixed_lds_doubles(int B) { return TRAIN_CHUNK * gng_rec_width(B) + 16 * 3 + 16 + 8 + 8; }
 
 // heapq.nlargest order: the larger value, ties to the earlier node (nan ln-probs are mapped to -inf before)
 __device__ __forceinline__ bool gng_better(double va, int ia, double vb, int ib) { return va > vb || (va == vb && ia < ib); }
@@ -69,15 +66,6 @@ __device__ __forceinline__ void gng_top_butterfly(GngTop& tp) {
     }
 }
 
-// np.argmax over the wave (som_better: the first nan wins, ties to the lower index)
-__device__ __forceinline__ void gng_argmax_butterfly(double& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
-        if (som_better(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-}
-
 // Stable in-place compaction of the rows of the surviving slots (newslot[s] >= 0, and <= s): every element moves to a lower or equal
 // index, so reading a block of NT elements, a barrier and then writing them never overwrites an element that is still to be read.
 template <class T>
@@ -97,7 +85,7 @@ __device__ __forceinline__ void gng_compact(T* arr, int width, int nslots, const
 }
 
 template <bool NODES_LDS>
-__global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
+__global__ __launch_bounds__(TRAIN_NT) void k_gng_train(GngArgs a) {
     extern __shared__ double s_gng[];
     const int t = threadIdx.x, NT = blockDim.x, lane = t & 63, wave = t >> 6, NW = NT >> 6;
     const int B = a.B, RW = gng_rec_width(B), CAP = a.cap, MD = a.md;
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
     int2* adj = reinterpret_cast<int2*>(gX + CAP);
     int* plist = reinterpret_cast<int*>(adj + 2 * (size_t)CAP * MD);
     int* age = plist + 3 * (size_t)a.pcap;
-    // LDS layout: [fit CAP*B] [err CAP] [deg CAP ints] [aux CAP ints] | recs GNG_CHUNK*RW | red 16*3 | redi 16*2 ints | scan 16 ints | sh 16 ints
+    // LDS layout: [fit CAP*B] [err CAP] [deg CAP ints] [aux CAP ints] | recs TRAIN_CHUNK*RW | red 16*3 | redi 16*2 ints | scan 16 ints | sh 16 ints
     double* base = s_gng;
     double *Y, *P, *E; int *D, *X;                                   // fit copy, graph positions, errors, degrees, aux (0 outside batch ends)
     if (NODES_LDS) {
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
     } else {
         P = gP; Y = a.track_scale ? gY : gP; E = gE; D = gD; X = gX;
     }
-    double* rec = base; base += GNG_CHUNK * RW;
+    double* rec = base; base += TRAIN_CHUNK * RW;
     double* red = base; base += 16 * 3;
     int* redi = reinterpret_cast<int*>(base); base += 16;
     int* sc = reinterpret_cast<int*>(base); base += 8;
@@ -136,28 +124,13 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
     __syncthreads();
     bool pend = false, stop = false;                                 // the previous step's error decay is still to be applied
 
-    for (int64_t c0 = a.s0; c0 < a.s1 && !stop; c0 += GNG_CHUNK) {
-        const int nc = (int)((a.s1 - c0) < GNG_CHUNK ? (a.s1 - c0) : GNG_CHUNK);
-        __syncthreads();                                             // the previous chunk's records are no longer read
-        for (int e = t; e < nc * B; e += NT) {
-            const int r = e / B, b = e - r * B;
-            const int64_t j = a.draws[c0 + r];
-            const double xe = a.xe[j * B + b];
-            double* R = rec + r * RW;
-            R[b] = a.x[j * B + b]; R[B + b] = xe * xe; R[2 * B + b] = a.xm[j * B + b];
-        }
-        if (t < nc) {
-            const int64_t j = a.draws[c0 + t];
-            const double* q = a.rowk + j * 4;
-            double* R = rec + t * RW + 3 * B;
-            R[0] = q[0]; R[1] = q[1]; R[2] = q[2]; R[3] = q[3];
-            R[4] = j == a.alias0 ? 0.0 : (j == a.alias1 ? 1.0 : -1.0);
-        }
-        __syncthreads();
+    for (int64_t c0 = a.s0; c0 < a.s1 && !stop; c0 += TRAIN_CHUNK) {
+        const int nc = (int)((a.s1 - c0) < TRAIN_CHUNK ? (a.s1 - c0) : TRAIN_CHUNK);
+        train_stage(a, c0, nc, rec, RW, t, NT, [&](int64_t, int64_t j, double* tail) { tail[0] = j == a.alias0 ? 0.0 : (j == a.alias1 ? 1.0 : -1.0); });
         for (int r = 0; r < nc && !stop; ++r) {
             const int64_t step = c0 + r;
             double* R = rec + r * RW;
-            const int al = (int)R[3 * B + 4];
+            const int al = (int)R[train_rec_head(B)];
             if (al >= 0) {
                 // the drawn row IS a node's position (the reference's initial nodes are views of the caller's rows): read it live;
                 // a removed node left its last position in the row
@@ -165,34 +138,14 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
                 if (t < B) R[t] = sl >= 0 ? P[(size_t)sl * B + t] : arow[al * B + t];
                 __syncthreads();
             }
-            const double* x = R; const double* tv = R + B; const double* m = R + 2 * B;
-            const double am1 = R[3 * B], G1 = R[3 * B + 1], G2 = R[3 * B + 2], K = R[3 * B + 3];
+            const TrainRow row = train_row(R, B);
             int NN = sh[GNG_NN];
             // ---- the previous step's error decay, node ln-probabilities, the track_scale rescale, the local top two ----
             GngTop tp; tp.v1 = -INFINITY; tp.c1 = 0.0; tp.v2 = -INFINITY; tp.i1 = 0x7fffffff; tp.i2 = 0x7fffffff;
             for (int n = t; n < NN; n += NT) {
                 if (pend) E[n] = E[n] * a.f_all;
-                double* y = Y + (size_t)n * B;
-                double chi2 = 0.0, s = 1.0;
-                if (a.free_scale) {
-                    double inter = 0.0, shape = 0.0;
-                    for (int b = 0; b < B; ++b) { const double yb = y[b]; inter += (m[b] * yb) * x[b] / tv[b]; shape += m[b] * (yb * yb) / tv[b]; }
-                    s = inter / shape;
-                    for (int b = 0; b < B; ++b) { const double d = x[b] - s * y[b]; chi2 += m[b] * (d * d) / tv[b]; }
-                } else {
-                    for (int b = 0; b < B; ++b) { const double d = x[b] - y[b]; chi2 += m[b] * (d * d) / tv[b]; }
-                }
-                double lnl;
-                if (a.dim_prior) {
-                    const double xl = (am1 == 0.0) ? ((chi2 == chi2) ? 0.0 : chi2) : am1 * log(chi2);     // xlogy
-                    lnl = ((xl - chi2 / 2.0) - G1) - G2;
-                } else {
-                    lnl = -0.5 * chi2 + K;
-                }
-                if (a.modec && !(s - s == 0.0)) lnl = NAN;                // as fz_som.h
-                if (a.track_scale) {                                      // networks.py:2171-2173
-                    for (int b = 0; b < B; ++b) y[b] = y[b] * s;
-                }
+                double chi2;
+                double lnl = train_lnl(a, row, Y + (size_t)n * B, chi2);
                 if (lnl != lnl) lnl = -INFINITY;                          // nan ln-probs count as the lowest (docs/deviations.md)
                 gng_merge(tp, lnl, n, chi2, -INFINITY, 0x7fffffff);
             }
@@ -210,7 +163,7 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
                 // ---- the best node (networks.py:2180-2184) ----
                 if (lane < B) {
                     const size_t o = (size_t)bmu * B + lane;
-                    const double d = a.learn_best * (x[lane] - P[o]);
+                    const double d = a.learn_best * (row.x[lane] - P[o]);
                     P[o] = P[o] + d;
                     if (a.track_scale) Y[o] = Y[o] + d;
                 }
@@ -244,7 +197,7 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
                     if (act) {
                         const size_t o = (size_t)ent.x * B;
                         for (int b = 0; b < B; ++b) {
-                            const double dd = a.learn_nbr * (x[b] - P[o + b]);
+                            const double dd = a.learn_nbr * (row.x[b] - P[o + b]);
                             P[o + b] = P[o + b] + dd;
                             if (a.track_scale) Y[o + b] = Y[o + b] + dd;
                         }
@@ -300,16 +253,12 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
                 for (int b0 = 0; b0 < NN; b0 += NT) {
                     const int n = b0 + t;
                     const bool alive = n < NN && X[n] != 2;
-                    const unsigned long long bal = __ballot(alive);
-                    const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-                    if (lane == 0) sc[wave] = __builtin_popcountll(bal);
-                    __syncthreads();
-                    int off = run, tot = 0;
-                    for (int w = 0; w < NW; ++w) { const int v = sc[w]; if (w < wave) off += v; tot += v; }
-                    if (n < NN) X[n] = alive ? off + pre : -1;
+                    int tot;
+                    const int ns = run + train_rank(alive, sc, lane, wave, NW, tot);
+                    if (n < NN) X[n] = alive ? ns : -1;
                     run += tot;
-                    __syncthreads();
                 }
+                __syncthreads();                                          // every new slot is written
                 if (t < 2) {                                              // the aliased rows follow their nodes
                     const int sl = sh[GNG_AL0 + t];
                     if (sl >= 0) {
@@ -340,20 +289,20 @@ __global__ __launch_bounds__(GNG_NT) void k_gng_train(GngArgs a) {
             } else if (NN < a.max_nodes) {
                 // ---- insertion (2221-2243): e1 = first arg-max of the errors, e2 = first arg-max among e1's neighbours ----
                 double bv = -INFINITY; int bix = 0x7fffffff;
-                for (int n = t; n < NN; n += NT) { const double v = E[n]; if (som_better(v, n, bv, bix)) { bv = v; bix = n; } }
-                gng_argmax_butterfly(bv, bix);
+                for (int n = t; n < NN; n += NT) { const double v = E[n]; if (train_better(v, n, bv, bix)) { bv = v; bix = n; } }
+                train_argmax_butterfly(bv, bix);
                 if (lane == 0) { red[wave] = bv; redi[wave] = bix; }
                 __syncthreads();
                 if (wave == 0) {
                     bv = -INFINITY; bix = 0x7fffffff;
                     if (lane < NW) { bv = red[lane]; bix = redi[lane]; }
-                    gng_argmax_butterfly(bv, bix);
+                    train_argmax_butterfly(bv, bix);
                     const int e1 = bix, ec = sh[GNG_EC];
                     const int d1 = D[e1];
                     int2 ent1 = make_int2(-1, -1);
                     double ev = -INFINITY; int ei = 0x7fffffff;
                     if (lane < d1) { ent1 = A[(size_t)e1 * MD + lane]; ev = E[ent1.x]; ei = lane; }
-                    gng_argmax_butterfly(ev, ei);
+                    train_argmax_butterfly(ev, ei);
                     const int k2 = ei, e2 = d1 ? __shfl(ent1.x, k2 & 63, 64) : e1;
                     const int d2 = D[e2];
                     int2 ent2 = make_int2(-1, -1);

@@ -1,13 +1,6 @@
 // ---- networks.py ABI: training of a growing neural gas (fz_gng.h) ---------------------------------------
 // Every array may live in host or device memory; host arrays are staged through the context's buffers (NetStage, fz_net_host.inc).
 namespace {
-template <bool LDSN>
-int gng_launch(fz_ctx* c, const fz::GngArgs& a, int nt, size_t lds) {
-    HIPCHK(hipFuncSetAttribute((const void*)fz::k_gng_train<LDSN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-    hipLaunchKernelGGL((fz::k_gng_train<LDSN>), dim3(1), dim3((unsigned)nt), lds, c->stream, a);
-    return 0;
-}
 // the sizes of the two state arrays (include/frankenz_hip.h gives the layout; networks._gng_state_sizes is the Python twin)
 int64_t gng_state_doubles(int32_t cap, int32_t B) { return 2 * (int64_t)cap * B + cap + 2 * (int64_t)B; }
 int64_t gng_state_ints(int32_t cap, int32_t max_degree, int32_t prune_cap, int32_t edge_cap) {
@@ -40,11 +33,7 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {models, models_err, models_mask, draws, fstate, istate, ids, bmus, batch}));
     // host-side checks that keep every device access in bounds: the drawn rows and the counters of the state
-    std::vector<int64_t> dr((size_t)(s1 - s0));
-    if (is_device_ptr(draws)) HIPCHK(hipMemcpy(dr.data(), draws + s0, dr.size() * 8, hipMemcpyDeviceToHost));
-    else std::memcpy(dr.data(), draws + s0, dr.size() * 8);
-    for (int64_t j : dr)
-        if (j < 0 || j >= M) return fail(-3, "fz_gng_train: drawn row %lld outside [0, %lld)", (long long)j, (long long)M);
+    FZCHK(check_draws("fz_gng_train", draws, s0, s1, M));
     int32_t cnt[GNG_NCNT];
     if (is_device_ptr(istate)) HIPCHK(hipMemcpy(cnt, istate, sizeof(cnt), hipMemcpyDeviceToHost));
     else std::memcpy(cnt, istate, sizeof(cnt));
@@ -53,11 +42,11 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
         cnt[fz::GNG_AL1] >= cap || (cnt[fz::GNG_CUR] & ~1))
         return fail(-4, "fz_gng_train: the state's counters are inconsistent (nodes %d of 2..%d, prune entries %d, edges %d, status %d)",
                     cnt[fz::GNG_NN], (int)cap, cnt[fz::GNG_NP], cnt[fz::GNG_EC], cnt[fz::GNG_STATUS]);
-    int lds_max = 0;
-    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    size_t lds_max;
+    FZCHK(train_lds_max(c, &lds_max));
     const size_t fixed = 8 * (size_t)fz::gng_fixed_lds_doubles(B);
     const size_t resident = 8 * ((size_t)cap * B + cap + 2 * (((size_t)cap + 1) / 2));
-    const bool lds_nodes = fixed + resident <= (size_t)lds_max;
+    const bool lds_nodes = fixed + resident <= lds_max;
     const size_t lds = fixed + (lds_nodes ? resident : 0);
     const int64_t nb = (T - 1) / nbatch + 1;
     const size_t nf = (size_t)gng_state_doubles(cap, B) * 8, ni = (size_t)gng_state_ints(cap, max_degree, prune_cap, edge_cap) * 4;
@@ -66,15 +55,8 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
     const void *d_x, *d_xe, *d_xm, *d_dr; void *d_f, *d_i, *d_ids, *d_bmus, *d_batch;
     FZCHK(st.in(models, (size_t)M * B * 8, &d_x)); FZCHK(st.in(models_err, (size_t)M * B * 8, &d_xe));
     FZCHK(st.in(models_mask, (size_t)M * B * 8, &d_xm)); FZCHK(st.in(draws, (size_t)T * 8, &d_dr));
-    FZCHK(st.out(fstate, nf, &d_f)); FZCHK(st.out(istate, ni, &d_i)); FZCHK(st.out(ids, (size_t)cap * 8, &d_ids));
-    FZCHK(st.out(bmus, (size_t)T * 8, &d_bmus)); FZCHK(st.out(batch, (size_t)nb * 2 * 4, &d_batch));
-    if (d_f != (void*)fstate) FZCHK(copy_in(c, d_f, fstate, nf));                                  // in/out
-    if (d_i != (void*)istate) FZCHK(copy_in(c, d_i, istate, ni));
-    if (d_ids != (void*)ids) FZCHK(copy_in(c, d_ids, ids, (size_t)cap * 8));
-    if (d_bmus != (void*)bmus) FZCHK(copy_in(c, d_bmus, bmus, (size_t)T * 8));                     // steps outside [s0, s1) keep their values
-    if (d_batch != (void*)batch) FZCHK(copy_in(c, d_batch, batch, (size_t)nb * 2 * 4));
-    FZCHK(c->d_net[9].ensure((size_t)M * 4 * 8));           // the per-row terms (k_som_rowk); slots 0..8 are the staging above
-    void* d_rowk = c->d_net[9].p;
+    FZCHK(st.inout(fstate, nf, &d_f)); FZCHK(st.inout(istate, ni, &d_i)); FZCHK(st.inout(ids, (size_t)cap * 8, &d_ids));
+    FZCHK(st.inout(bmus, (size_t)T * 8, &d_bmus)); FZCHK(st.inout(batch, (size_t)nb * 2 * 4, &d_batch));   // steps outside [s0, s1) keep their values
 
     fz::GngArgs a;
     a.x = (const double*)d_x; a.xe = (const double*)d_xe; a.xm = (const double*)d_xm; a.draws = (const int64_t*)d_dr;
@@ -85,15 +67,7 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
     a.learn_best = learn_best; a.learn_nbr = learn_neighbor; a.f_new = new_err_keep; a.f_all = all_err_keep;
     a.free_scale = opts->free_scale ? 1 : 0; a.dim_prior = opts->dim_prior ? 1 : 0;
     a.modec = (opts->free_scale && !opts->ignore_model_err) ? 1 : 0; a.track_scale = track_scale ? 1 : 0;
-    const int nt = cap >= GNG_NT ? GNG_NT : ((cap + 63) / 64) * 64;
-    const int nrowk = (int)((M + 255) / 256);
-    hipLaunchKernelGGL(fz::k_som_rowk, dim3((unsigned)nrowk), dim3(256), 0, c->stream, a.xe, a.xm, M, (int)B, a.free_scale, (double*)d_rowk);
-    a.rowk = (const double*)d_rowk;
-    const int rc = lds_nodes ? gng_launch<true>(c, a, nt, lds) : gng_launch<false>(c, a, nt, lds);
-    FZCHK(rc);
-    HIPCHK(hipGetLastError());
-    FZCHK(st.finish());
-    HIPCHK(hipStreamSynchronize(c->stream));
+    FZCHK(lds_nodes ? train_run(c, st, fz::k_gng_train<true>, a, M, cap, lds) : train_run(c, st, fz::k_gng_train<false>, a, M, cap, lds));
     HIPCHK(hipMemcpy(cnt, d_i, sizeof(cnt), hipMemcpyDeviceToHost));
     switch (cnt[fz::GNG_STATUS]) {
         case fz::GNG_OK: return 0;

@@ -26,6 +26,11 @@ struct NetStage {
         outs.push_back({p, b.p, bytes});
         return 0;
     }
+    // out() whose staged copy starts as the caller's array: in/out arrays, and outputs only part of which is written
+    int inout(void* p, size_t bytes, void** dev) {
+        FZCHK(out(p, bytes, dev));
+        return *dev != p ? copy_in(c, *dev, p, bytes) : 0;
+    }
     int finish() {
         for (auto& o : outs) FZCHK(copy_out(c, o.host, o.dev, o.bytes));
         return 0;

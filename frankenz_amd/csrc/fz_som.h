@@ -4,22 +4,21 @@
 // nodes by the wt_thresh or the CDF rule and moves them towards the row.  Every node is owned by ONE thread for the whole launch
 // (node n by thread n mod NT), so the node work of a step needs no barrier; the BMU reduction is the one barrier of a step under the
 // wt_thresh rule (five under the CDF rule).  The nodes and their grid positions live in LDS when they fit (NODES_LDS), otherwise in
-// global memory, still owned by the one workgroup.  Draw indices, learning rates and sigmas are host tables; the rows of SOM_CHUNK
-// steps are staged into LDS together (one exposed global-load latency per chunk instead of per step).  docs/som.md.
+// global memory, still owned by the one workgroup.  Draw indices, learning rates and sigmas are host tables; the rows of TRAIN_CHUNK
+// steps are staged into LDS together (one exposed global-load latency per chunk instead of per step).  The staging, the
+// ln-probability and the arg-max order are fz_train.h's, shared with the growing neural gas.  docs/som.md.
 #pragma once
-#include "fz_device.h"
+#include "fz_train.h"
 
 namespace fz {
 
-#define SOM_CHUNK 32        // steps whose rows are staged into LDS at once
-#define SOM_NT 1024         // threads of the workgroup (at most)
 #define SOM_MAXPROJ 8       // grid dimensions
 
 struct SomArgs {
     const double* x;        // (M, B) cleaned model values
     const double* xe;       // (M, B) cleaned model errors
     const double* xm;       // (M, B) cleaned mask (0/1)
-    const double* rowk;     // (M, 4) k_som_rowk: am1, gammaln(a), ln2 a, -0.5 (Ndim ln 2pi + sum log tot_var)
+    const double* rowk;     // (M, 4) k_train_rowk
     double* nodes;          // (NNODE, B) in/out
     const int32_t* pos;     // (NNODE, NPROJ) integer grid positions
     const int64_t* draws;   // (T) row drawn at each step
@@ -35,43 +34,21 @@ struct SomArgs {
     int dmax;               // largest squared grid distance (CDF rule: histogram bins 0..dmax)
 };
 
-// per-step record staged in LDS: x[B] tv[B] m[B] am1 G1 G2 K lr sig
-__host__ __device__ constexpr int som_rec_width(int B) { return 3 * B + 6; }
+// per-step record staged in LDS: the head (fz_train.h), then lr sig
+__host__ __device__ constexpr int som_rec_width(int B) { return train_rec_head(B) + 2; }
+// the LDS of k_som_train besides the resident nodes and the CDF rule's histogram, in doubles: recs | red 2*2*16 | scan 16*2 | bnd 4
+__host__ __device__ constexpr int som_fixed_lds_doubles(int B) { return TRAIN_CHUNK * som_rec_width(B) + 32 + 16 + 16 + 8 + 4; }
 
 __device__ __forceinline__ double som_weight(int kind, double d, double s2) {
     return kind == 0 ? exp(-0.5 * d / s2) : s2 / (d + s2);        // networks.py:81, 111: the reference's operation order
 }
 
-// np.argmax order: the first nan wins, else the larger value, ties to the lower index
-__device__ __forceinline__ bool som_better(double va, int ia, double vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na || nb) return na && (!nb || ia < ib);
-    return va > vb || (va == vb && ia < ib);
-}
-
-// The terms of a row's ln-likelihood that are the same for every node (pdf.py:90-98, 226-235): ym = 1, so Ndim = sum(xm), and
-// tot_var = xe^2 (+ 0^2) in every mode.  One thread per model row, once per launch of k_som_train (lgamma kept out of its loop).
-__global__ __launch_bounds__(256) void k_som_rowk(const double* __restrict__ xe, const double* __restrict__ xm, int64_t M, int B,
-                                                  int free_scale, double* __restrict__ rowk) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= M) return;
-    double nd = 0.0, slv = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const double e = xe[j * B + b];
-        nd += xm[j * B + b];
-        slv += log(e * e);
-    }
-    const double av = free_scale ? 0.5 * (nd - 1.0) : 0.5 * nd;
-    rowk[j * 4 + 0] = av - 1.0; rowk[j * 4 + 1] = lgamma(av); rowk[j * 4 + 2] = FZ_LN2 * av;
-    rowk[j * 4 + 3] = -0.5 * (nd * FZ_LN2PI + slv);
-}
-
 template <bool NODES_LDS>
-__global__ __launch_bounds__(SOM_NT) void k_som_train(SomArgs a) {
+__global__ __launch_bounds__(TRAIN_NT) void k_som_train(SomArgs a) {
     extern __shared__ double s_som[];
     const int t = threadIdx.x, NT = blockDim.x, lane = t & 63, wave = t >> 6, NW = NT >> 6;
     const int B = a.B, RW = som_rec_width(B), NN = a.nnode, NP = a.nproj;
-    // LDS layout: [nodes NN*B] [pos NN*NP ints, padded to doubles] | recs SOM_CHUNK*RW | red 2*2*16 | scan 16*2 | bnd 4 | hist
+    // LDS layout: [nodes NN*B] [pos NN*NP ints, padded to doubles] | som_fixed_lds_doubles(B): recs, red, scan, bnd | hist
     double* base = s_som;
     double* Y = a.nodes;
     const int32_t* P = a.pos;
@@ -82,7 +59,7 @@ __global__ __launch_bounds__(SOM_NT) void k_som_train(SomArgs a) {
         for (int e = t; e < NN * B; e += NT) Y[e] = a.nodes[e];
         for (int e = t; e < NN * NP; e += NT) Pw[e] = a.pos[e];
     }
-    double* rec = base; base += SOM_CHUNK * RW;
+    double* rec = base; base += TRAIN_CHUNK * RW;
     double* redv = base; base += 2 * 16;                         // BMU: value per wave, two buffers (step parity)
     int* redi = reinterpret_cast<int*>(base); base += 16;        //      index per wave (2 * 16 ints)
     double* scw = base; base += 16;                              // CDF: weight sum per wave
@@ -93,69 +70,29 @@ __global__ __launch_bounds__(SOM_NT) void k_som_train(SomArgs a) {
     const int bpt = (nbins + NT - 1) / NT;                       // bins per thread (the thread's bins are contiguous)
     for (int e = t; e < nbins; e += NT) hist[e] = 0;
 
-    for (int64_t c0 = a.s0; c0 < a.s1; c0 += SOM_CHUNK) {
-        const int nc = (int)((a.s1 - c0) < SOM_CHUNK ? (a.s1 - c0) : SOM_CHUNK);
-        __syncthreads();                                         // the previous chunk's records are no longer read
-        for (int e = t; e < nc * B; e += NT) {
-            const int r = e / B, b = e - r * B;
-            const int64_t j = a.draws[c0 + r];
-            const double xe = a.xe[j * B + b];
-            double* R = rec + r * RW;
-            R[b] = a.x[j * B + b]; R[B + b] = xe * xe; R[2 * B + b] = a.xm[j * B + b];
-        }
-        if (t < nc) {
-            const double* q = a.rowk + a.draws[c0 + t] * 4;
-            double* R = rec + t * RW + 3 * B;
-            R[0] = q[0]; R[1] = q[1]; R[2] = q[2]; R[3] = q[3];
-            R[4] = a.lr[c0 + t]; R[5] = a.sig[c0 + t];
-        }
-        __syncthreads();
+    for (int64_t c0 = a.s0; c0 < a.s1; c0 += TRAIN_CHUNK) {
+        const int nc = (int)((a.s1 - c0) < TRAIN_CHUNK ? (a.s1 - c0) : TRAIN_CHUNK);
+        train_stage(a, c0, nc, rec, RW, t, NT, [&](int64_t step, int64_t, double* tail) { tail[0] = a.lr[step]; tail[1] = a.sig[step]; });
         for (int r = 0; r < nc; ++r) {
             const int64_t step = c0 + r;
             const double* R = rec + r * RW;
-            const double* x = R; const double* tv = R + B; const double* m = R + 2 * B;
-            const double am1 = R[3 * B], G1 = R[3 * B + 1], G2 = R[3 * B + 2], K = R[3 * B + 3];
-            const double lr = R[3 * B + 4], sg = R[3 * B + 5];
+            const TrainRow row = train_row(R, B);
+            const double lr = R[train_rec_head(B)], sg = R[train_rec_head(B) + 1];
             // ---- node ln-probabilities, the track_scale rescale, the local argmax ----
             double bv = -INFINITY; int bi = 0x7fffffff;
             for (int n = t; n < NN; n += NT) {
-                double* y = Y + (size_t)n * B;
-                double chi2 = 0.0, s = 1.0;
-                if (a.free_scale) {
-                    double inter = 0.0, shape = 0.0;
-                    for (int b = 0; b < B; ++b) { const double yb = y[b]; inter += (m[b] * yb) * x[b] / tv[b]; shape += m[b] * (yb * yb) / tv[b]; }
-                    s = inter / shape;
-                    for (int b = 0; b < B; ++b) { const double d = x[b] - s * y[b]; chi2 += m[b] * (d * d) / tv[b]; }
-                } else {
-                    for (int b = 0; b < B; ++b) { const double d = x[b] - y[b]; chi2 += m[b] * (d * d) / tv[b]; }
-                }
-                double lnl;
-                if (a.dim_prior) {
-                    const double xl = (am1 == 0.0) ? ((chi2 == chi2) ? 0.0 : chi2) : am1 * log(chi2);     // xlogy
-                    lnl = ((xl - chi2 / 2.0) - G1) - G2;
-                } else {
-                    lnl = -0.5 * chi2 + K;
-                }
-                // mode C with noiseless nodes: the second pass of pdf.py:199-222 repeats the first exactly, except that a
-                // non-finite scale makes tot_var = xe^2 + (s * 0)^2 nan
-                if (a.modec && !(s - s == 0.0)) lnl = NAN;
-                if (a.track_scale) {                                      // networks.py:1838-1840
-                    for (int b = 0; b < B; ++b) y[b] = y[b] * s;
-                }
-                if (som_better(lnl, n, bv, bi)) { bv = lnl; bi = n; }
+                double chi2;
+                const double lnl = train_lnl(a, row, Y + (size_t)n * B, chi2);
+                if (train_better(lnl, n, bv, bi)) { bv = lnl; bi = n; }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-                if (som_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
+            train_argmax_butterfly(bv, bi);
             const int par = (int)(step & 1);
             if (lane == 0) { redv[par * 16 + wave] = bv; redi[par * 16 + wave] = bi; }
             __syncthreads();
             bv = redv[par * 16]; bi = redi[par * 16];
             for (int w = 1; w < NW; ++w) {
                 const double ov = redv[par * 16 + w]; const int oi = redi[par * 16 + w];
-                if (som_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+                if (train_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
             }
             const int bmu = bi;
             if (t == 0) a.bmus[step] = bmu;
@@ -256,20 +193,15 @@ __global__ __launch_bounds__(SOM_NT) void k_som_train(SomArgs a) {
                     else { keep = w < wB; ingrp = (w == wB); if (ingrp && !straddle) keep = kgrp > 0; }
                 }
                 if (straddle) {                                       // uniform branch
-                    const unsigned long long bal = __ballot(ingrp);
-                    const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-                    if (lane == 0) scc[wave] = __builtin_popcountll(bal);
-                    __syncthreads();
-                    int off = rank_base, tot = 0;
-                    for (int w2 = 0; w2 < NW; ++w2) { const int v = scc[w2]; if (w2 < wave) off += v; tot += v; }
-                    if (ingrp) keep = off + pre < kgrp;
+                    int tot;
+                    const int rk = rank_base + train_rank(ingrp, scc, lane, wave, NW, tot);
+                    if (ingrp) keep = rk < kgrp;
                     rank_base += tot;
-                    __syncthreads();
                 }
                 if (keep) {
                     double* y = Y + (size_t)n * B;
                     const double f = lr * w;
-                    for (int b = 0; b < B; ++b) y[b] = y[b] + f * (x[b] - y[b]);
+                    for (int b = 0; b < B; ++b) y[b] = y[b] + f * (row.x[b] - y[b]);
                 }
             }
         }

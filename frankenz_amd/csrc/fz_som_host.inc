@@ -1,15 +1,5 @@
 // ---- networks.py ABI: training of a self-organizing map (fz_som.h) -------------------------------------
 // Every array may live in host or device memory; host arrays are staged through the context's buffers (NetStage, fz_net_host.inc).
-namespace {
-template <bool LDSN>
-int som_launch(fz_ctx* c, const fz::SomArgs& a, int nt, size_t lds) {
-    HIPCHK(hipFuncSetAttribute((const void*)fz::k_som_train<LDSN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-    hipLaunchKernelGGL((fz::k_som_train<LDSN>), dim3(1), dim3((unsigned)nt), lds, c->stream, a);
-    return 0;
-}
-}  // namespace
-
 extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* models_err, const double* models_mask, int64_t M, int32_t B,
                             double* nodes, const int32_t* nodes_pos, int32_t NNODE, int32_t NPROJ, const int64_t* draws,
                             const double* learn_rate, const double* sigma, int64_t T, int32_t neighbor_kind, int32_t use_wt,
@@ -29,11 +19,7 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {models, models_err, models_mask, nodes, nodes_pos, draws, learn_rate, sigma, bmus}));
     // host-side checks that keep every device access in bounds: the drawn rows, and the squared-distance range (CDF histogram)
-    std::vector<int64_t> dr((size_t)(s1 - s0));
-    if (is_device_ptr(draws)) HIPCHK(hipMemcpy(dr.data(), draws + s0, dr.size() * 8, hipMemcpyDeviceToHost));
-    else std::memcpy(dr.data(), draws + s0, dr.size() * 8);
-    for (int64_t j : dr)
-        if (j < 0 || j >= M) return fail(-3, "fz_som_train: drawn row %lld outside [0, %lld)", (long long)j, (long long)M);
+    FZCHK(check_draws("fz_som_train", draws, s0, s1, M));
     std::vector<int32_t> pos((size_t)NNODE * NPROJ);
     if (is_device_ptr(nodes_pos)) HIPCHK(hipMemcpy(pos.data(), nodes_pos, pos.size() * 4, hipMemcpyDeviceToHost));
     else std::memcpy(pos.data(), nodes_pos, pos.size() * 4);
@@ -43,15 +29,15 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
         for (int32_t n = 0; n < NNODE; ++n) { const int32_t v = pos[(size_t)n * NPROJ + p]; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
         dmax += ((double)hi - lo) * ((double)hi - lo);
     }
-    int lds_max = 0;
-    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    const size_t fixed = 8 * ((size_t)SOM_CHUNK * fz::som_rec_width(B) + 32 + 16 + 16 + 8 + 4);
+    size_t lds_max;
+    FZCHK(train_lds_max(c, &lds_max));
+    const size_t fixed = 8 * (size_t)fz::som_fixed_lds_doubles(B);
     const size_t hist = use_wt ? 0 : 4 * ((size_t)dmax + 1);
-    if (fixed + hist > (size_t)lds_max)
+    if (fixed + hist > lds_max)
         return fail(-5, "fz_som_train: the CDF rule keeps a histogram of the %.0f squared grid distances in LDS; at most %zu fit", dmax + 1,
-                    ((size_t)lds_max - fixed) / 4);
+                    (lds_max - fixed) / 4);
     const size_t resident = 8 * (size_t)NNODE * B + 8 * (((size_t)NNODE * NPROJ + 1) / 2);
-    const bool lds_nodes = fixed + hist + resident <= (size_t)lds_max;
+    const bool lds_nodes = fixed + hist + resident <= lds_max;
     const size_t lds = fixed + hist + (lds_nodes ? resident : 0);
 
     NetStage st{c};
@@ -59,12 +45,8 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
     FZCHK(st.in(models, (size_t)M * B * 8, &d_x)); FZCHK(st.in(models_err, (size_t)M * B * 8, &d_xe));
     FZCHK(st.in(models_mask, (size_t)M * B * 8, &d_xm)); FZCHK(st.in(nodes_pos, pos.size() * 4, &d_pos));
     FZCHK(st.in(draws, (size_t)T * 8, &d_dr)); FZCHK(st.in(learn_rate, (size_t)T * 8, &d_lr)); FZCHK(st.in(sigma, (size_t)T * 8, &d_sig));
-    FZCHK(st.out(nodes, (size_t)NNODE * B * 8, &d_nodes));
-    if (d_nodes != (void*)nodes) FZCHK(copy_in(c, d_nodes, nodes, (size_t)NNODE * B * 8));          // in/out
-    FZCHK(st.out(bmus, (size_t)T * 4, &d_bmus));
-    FZCHK(c->d_net[9].ensure((size_t)M * 4 * 8));           // the per-row terms (k_som_rowk); slots 0..8 are the staging above
-    void* d_rowk = c->d_net[9].p;
-    if (d_bmus != (void*)bmus) FZCHK(copy_in(c, d_bmus, bmus, (size_t)T * 4));                  // steps outside [s0, s1) keep their values
+    FZCHK(st.inout(nodes, (size_t)NNODE * B * 8, &d_nodes));
+    FZCHK(st.inout(bmus, (size_t)T * 4, &d_bmus));                                              // steps outside [s0, s1) keep their values
 
     fz::SomArgs a;
     a.x = (const double*)d_x; a.xe = (const double*)d_xe; a.xm = (const double*)d_xm; a.nodes = (double*)d_nodes;
@@ -73,14 +55,5 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
     a.use_wt = use_wt ? 1 : 0; a.wt_thresh = wt_thresh; a.cdf_thresh = cdf_thresh;
     a.free_scale = opts->free_scale ? 1 : 0; a.dim_prior = opts->dim_prior ? 1 : 0;
     a.modec = (opts->free_scale && !opts->ignore_model_err) ? 1 : 0; a.track_scale = track_scale ? 1 : 0; a.dmax = (int)dmax;
-    const int nt = NNODE >= SOM_NT ? SOM_NT : ((NNODE + 63) / 64) * 64;
-    const int nrowk = (int)((M + 255) / 256);
-    hipLaunchKernelGGL(fz::k_som_rowk, dim3((unsigned)nrowk), dim3(256), 0, c->stream, a.xe, a.xm, M, (int)B, a.free_scale, (double*)d_rowk);
-    a.rowk = (const double*)d_rowk;
-    const int rc = lds_nodes ? som_launch<true>(c, a, nt, lds) : som_launch<false>(c, a, nt, lds);
-    FZCHK(rc);
-    HIPCHK(hipGetLastError());
-    FZCHK(st.finish());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return lds_nodes ? train_run(c, st, fz::k_som_train<true>, a, M, NNODE, lds) : train_run(c, st, fz::k_som_train<false>, a, M, NNODE, lds);
 }

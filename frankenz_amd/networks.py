@@ -77,13 +77,9 @@ def _select(eng, lnprob, wt_thresh, cdf_thresh, match=None, csr_off=None, want_s
 
 def _lists_from_plane(lnprob, scale, scale_err, wt_thresh, cdf_thresh, track_scale, eng=None):
     """the (Nmodels, Nnodes) ln-prob plane -> the per-model selections and the per-node lists"""
-    Nmodels, Nnodes = lnprob.shape
-    out = NetworkMap()
     # The selection of every model's nodes (either rule, in the reference's order) and the max / logsumexp over the kept entries
     # come from the device (fz_net_select, networks.py:316-333); what follows is the transpose of the kept (model, node) pairs into
     # per-node lists -- models ascending inside a node, as the reference's model loop appends them.
-    rows = np.arange(Nmodels)
-    out.models_bmu = np.argmax(lnprob, axis=1)                       # best-matching unit per model
     eng = eng if eng is not None else get_engine(None)
     nsel, sel, _, lmap, levid = _select(eng, np.ascontiguousarray(lnprob), wt_thresh, cdf_thresh, want_stats=True)
     return _lists_from_selection(lnprob, scale, scale_err, nsel, sel, lmap, levid, track_scale)
@@ -161,6 +157,13 @@ class Network(object):
             self.nodes_pos = np.asarray(nodes_pos)
             self.NPROJ = self.nodes_pos.shape[1]
         return self
+
+    def _training_models(self, models, models_err, models_mask, err_kernel):
+        """the arrays ``train_network`` fits: the given ones, by default the object's own, ``err_kernel`` added to the errors"""
+        models_err = _given(models_err, self.models_err)
+        if err_kernel is not None:
+            models_err = np.sqrt(models_err**2 + err_kernel**2)          # added in quadrature
+        return _given(models, self.models), models_err, _given(models_mask, self.models_mask)
 
     def _eng(self):
         return get_engine(self._device)
@@ -587,12 +590,41 @@ def _given(value, default):
     return default if value is None else value
 
 
+def _training_opts(lprob_kwargs, track_scale):
+    """the likelihood options of a device training run; track_scale needs the scale back"""
+    opts = like_opts(lprob_kwargs)
+    if track_scale and not (opts.free_scale and lprob_kwargs.get('return_scale', False)):
+        raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True, return_scale=True)")
+    return opts
+
+
+def _training_inputs(rstate, models, models_err, models_mask, T):
+    """The inputs of a device training run: the rows drawn at the T steps (rstate.choice per step) and fp64 copies of the models
+    cleaned up front (pdf.py:309-311).  The reference cleans every drawn row of the caller's arrays in place, and so do we, once,
+    before the run."""
+    draws = _draw_stream(rstate, len(models), T)
+    x, xe, xm = (np.array(a, dtype=np.float64, order='C') for a in (models, models_err, models_mask))
+    _clean_rows(x, xe, xm, np.arange(len(models)))
+    _clean_rows(models, models_err, models_mask, np.unique(draws))
+    return draws, x, xe, xm
+
+
+def _device_arrays(device, arrays):
+    """device copies of the training arrays (torch on this engine's GPU), so that the network stays on the device between launches;
+    without torch the library stages the host arrays itself"""
+    try:
+        import torch
+        if not torch.cuda.is_available():
+            return arrays
+    except ImportError:
+        return arrays
+    d = torch.device('cuda', device)
+    return tuple(torch.from_numpy(a).to(d) for a in arrays)
+
+
 class SelfOrganizingMap(Network):
     """The reference's ``SelfOrganizingMap``: ``train_network`` runs on the device (``fz_som_train``, one persistent workgroup per
     map, docs/som.md); inference is the inherited ``Network``."""
-
-    def __init__(self, models, models_err, models_mask, device=None):
-        super(SelfOrganizingMap, self).__init__(models, models_err, models_mask, device=device)
 
     def train_network(self, models=None, models_err=None, models_mask=None, nside=50, nproj=2, nodes_init=None, niter=2000,
                       nbatch=50, err_kernel=None, lprob_func=None, learn_func=None, neighbor_func=None, wt_thresh=1e-3,
@@ -601,11 +633,7 @@ class SelfOrganizingMap(Network):
         """Fit ``nside**nproj`` nodes on an ``nproj``-dimensional grid to the models (by default the ones the map was built with)
         over ``niter * nbatch`` steps.  Keywords and defaults are the reference's (networks.py:1517-1681); afterwards ``nodes``,
         ``nodes_pos``, ``NSIDE``, ``NNODE``, ``NPROJ``, ``NITER`` and ``NBATCH`` hold the trained map."""
-        models = _given(models, self.models)
-        models_err = _given(models_err, self.models_err)
-        models_mask = _given(models_mask, self.models_mask)
-        if err_kernel is not None:
-            models_err = np.sqrt(models_err**2 + err_kernel**2)          # added in quadrature
+        models, models_err, models_mask = self._training_models(models, models_err, models_mask, err_kernel)
         steps = self._train_network(models, models_err, models_mask, lprob_func=lprob_func, nside=nside, nproj=nproj,
                                     nodes_init=nodes_init, learn_func=learn_func, neighbor_func=neighbor_func, niter=niter,
                                     nbatch=nbatch, wt_thresh=wt_thresh, cdf_thresh=cdf_thresh, rstate=rstate, lprob_args=lprob_args,
@@ -640,8 +668,7 @@ class SelfOrganizingMap(Network):
         self.NSIDE, self.NNODE, self.NPROJ = nside, nside**nproj, nproj
         self.nodes_pos = som_nodes_pos(nside, nproj)
         # initial nodes: distinct model rows as they stand (before any cleaning), or nodes_init itself, which is then trained in place
-        Nmodel = len(models)
-        self.nodes = np.array(models[rstate.choice(Nmodel, size=self.NNODE, replace=False)]) if nodes_init is None else nodes_init
+        self.nodes = np.array(models[rstate.choice(len(models), size=self.NNODE, replace=False)]) if nodes_init is None else nodes_init
 
         if not (_is_default(lprob_func) and not lprob_args and neighbor_func in (neighbor_gauss, neighbor_lorentz)):
             for step in self._som_host_steps(models, models_err, models_mask, times, rstate, lprob_func, lprob_args, lprob_kwargs,
@@ -650,19 +677,11 @@ class SelfOrganizingMap(Network):
                 yield step
             return
 
-        opts = like_opts(lprob_kwargs)
-        if track_scale and not (opts.free_scale and lprob_kwargs.get('return_scale', False)):
-            raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True, return_scale=True)")
-        # the tables of the whole run: draws (rstate.choice per step), learning rates, sigmas
-        draws = _draw_stream(rstate, Nmodel, T)
+        opts = _training_opts(lprob_kwargs, track_scale)
+        draws, x, xe, xm = _training_inputs(rstate, models, models_err, models_mask, T)
+        # the other tables of the whole run: learning rates, sigmas
         lr = _learn_table(learn_func, times, learn_args, learn_kwargs)
         sig = _sigma_table(neighbor_func, times, self.NSIDE, neighbor_args, neighbor_kwargs)
-        # the models cleaned up front (pdf.py:309-311); the reference cleans every drawn row of the caller's arrays in place, and so
-        # do we, once, before the run
-        x, xe = np.array(models, dtype=np.float64, order='C'), np.array(models_err, dtype=np.float64, order='C')
-        xm = np.array(models_mask, dtype=np.float64, order='C')
-        _clean_rows(x, xe, xm, np.arange(Nmodel))
-        _clean_rows(models, models_err, models_mask, np.unique(draws))
         nodes = np.array(self.nodes, dtype=np.float64, order='C')
         if nodes.shape != (self.NNODE, x.shape[1]):
             raise ValueError("nodes_init must have shape (nside**nproj, Nfilt) = %r" % ((self.NNODE, x.shape[1]),))
@@ -671,8 +690,7 @@ class SelfOrganizingMap(Network):
         eng = self._eng()
         kind = 0 if neighbor_func is neighbor_gauss else 1
         use_wt = wt_thresh is not None
-        dev = _som_device_arrays(eng.device, (x, xe, xm, nodes, pos, draws, lr, sig, bmus))
-        dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, dbmus = dev
+        dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, dbmus = _device_arrays(eng.device, (x, xe, xm, nodes, pos, draws, lr, sig, bmus))
         seg = max(1, int(_SOM_SEGMENT))
         for s0 in range(0, T, seg):
             s1 = min(T, s0 + seg)
@@ -707,19 +725,6 @@ class SelfOrganizingMap(Network):
             moved = _som_selection(wts, wt_thresh, cdf_thresh)
             nodes[moved] += rate * wts[moved, None] * (models[row] - nodes[moved])
             yield fits, best, rate, width
-
-
-def _som_device_arrays(device, arrays):
-    """device copies of the training arrays (torch on this engine's GPU), so that the map stays on the device between launches;
-    without torch the library stages the host arrays itself"""
-    try:
-        import torch
-        if not torch.cuda.is_available():
-            return arrays
-    except ImportError:
-        return arrays
-    d = torch.device('cuda', device)
-    return tuple(torch.from_numpy(a).to(d) for a in arrays)
 
 
 # ---- training of a growing neural gas (reference networks.py:1870-2260) --------------------------------------------------------------
@@ -785,11 +790,7 @@ class GrowingNeuralGas(Network):
         """Grow a network of at most ``max_nodes`` nodes on the models (by default the ones the object was built with) over
         ``niter * nbatch`` steps.  Keywords and defaults are the reference's (networks.py:1898-2035); afterwards ``nodes``,
         ``NNODE``, ``graph`` and the ``graph_*`` arrays hold the trained network."""
-        models = _given(models, self.models)
-        models_err = _given(models_err, self.models_err)
-        models_mask = _given(models_mask, self.models_mask)
-        if err_kernel is not None:
-            models_err = np.sqrt(models_err**2 + err_kernel**2)          # added in quadrature
+        models, models_err, models_mask = self._training_models(models, models_err, models_mask, err_kernel)
         steps = self._train_network(models, models_err, models_mask, learn_best=learn_best, learn_neighbor=learn_neighbor,
                                     max_age=max_age, nbatch=nbatch, new_err_dec=new_err_dec, all_err_dec=all_err_dec,
                                     max_nodes=max_nodes, niter=niter, graph_init=graph_init, lprob_func=lprob_func, rstate=rstate,
@@ -825,9 +826,7 @@ class GrowingNeuralGas(Network):
                                           "device (at most %d)" % (max(int(max_nodes), nn0), _GNG_MAX_NODES))
             if T >= 1 << 30:
                 raise NotImplementedError("GrowingNeuralGas.train_network: %d steps unsupported on the device (below 2**30)" % T)
-            opts = like_opts(lprob_kwargs)
-            if track_scale and not (opts.free_scale and lprob_kwargs.get('return_scale', False)):
-                raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True, return_scale=True)")
+            opts = _training_opts(lprob_kwargs, track_scale)
         if nn0 < 2:
             raise ValueError("graph_init needs at least two nodes")
 
@@ -858,12 +857,7 @@ class GrowingNeuralGas(Network):
                 yield step
             return
 
-        draws = _draw_stream(rstate, Nmodel, T)
-        # the models cleaned up front (pdf.py:309-311), the drawn rows of the caller's arrays too, as in the SOM path
-        x, xe = np.array(models, dtype=np.float64, order='C'), np.array(models_err, dtype=np.float64, order='C')
-        xm = np.array(models_mask, dtype=np.float64, order='C')
-        _clean_rows(x, xe, xm, np.arange(Nmodel))
-        _clean_rows(models, models_err, models_mask, np.unique(draws))
+        draws, x, xe, xm = _training_inputs(rstate, models, models_err, models_mask, T)
         # ---- the state arrays (include/frankenz_hip.h) ----
         md = int(_GNG_MAX_DEGREE)
         cap = max(int(max_nodes), nn0)
@@ -900,8 +894,7 @@ class GrowingNeuralGas(Network):
         idv = np.zeros(cap, dtype=np.int64); idv[:nn0] = ids
         bmus, batch = np.zeros(max(T, 1), dtype=np.int64), np.zeros((max(nbatches, 1), 2), dtype=np.int32)
         eng = self._eng()
-        dev = _som_device_arrays(eng.device, (x, xe, xm, draws, fst, ist, idv, bmus, batch))
-        dx, dxe, dxm, ddraws, dfst, dist, dids, dbmus, dbatch = dev
+        dx, dxe, dxm, ddraws, dfst, dist, dids, dbmus, dbatch = _device_arrays(eng.device, (x, xe, xm, draws, fst, ist, idv, bmus, batch))
         host = lambda a_: a_ if isinstance(a_, np.ndarray) else a_.cpu().numpy()
         seg = max(1, int(_GNG_SEGMENT))
         for s0 in range(0, T, seg):
