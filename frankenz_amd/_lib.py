@@ -121,6 +121,9 @@ ABI = {
                                                        C.POINTER(KdeOpts), C.POINTER(PriorLerp)] + [_P] * 12),
     "fz_knn_fit_predict_prior_lerp": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, C.POINTER(LikeOpts),
                                                 C.POINTER(KdeOpts), C.POINTER(PriorLerp)] + [_P] * 12),
+    "fz_stack2d": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _F64, _I32, _I32, _I32, _P]),
+    "fz_recentre_rows": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I64, _P, _P]),
+    "fz_cdf_draws": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
     "fz_prior_rows_from_grid": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
 }
 

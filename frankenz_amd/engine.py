@@ -402,6 +402,24 @@ class Engine(object):
         check(self.lib.fz_overlap_nz(self.h, ptr(pdfs), n, len(nz), ptr(nz), pi, pj, float(step), ptr(overlap), ptr(out)))
         return float(out[0])
 
+    # -- validation of a PDF stack (plotting.py; fz_diag.h) ---------------------
+    def stack2d(self, pdfs, nrows, Gy, rows, cent, eidx, weff, pdf_thresh, prepared, stack, full_range=False, accumulate=False):
+        """fz_stack2d over the dictionary last uploaded: ``rows`` / ``cent`` / ``eidx`` (int64) and ``weff`` (float64) are host
+        arrays of the selected objects in ascending order of ``cent``; ``stack`` (Gx, Gy) is written, or added to"""
+        check(self.lib.fz_stack2d(self.h, ptr(pdfs), int(nrows), int(Gy), len(rows), ptr(rows), ptr(cent), ptr(eidx), ptr(weff),
+                                  float(pdf_thresh), int(bool(prepared)), int(bool(full_range)), int(bool(accumulate)), ptr(stack)))
+
+    def recentre_rows(self, pdfs, n, pgrid, cent, disp, dgrid, out):
+        """fz_recentre_rows: ``out`` (n, len(dgrid)) = every row resampled around its own centre (``disp`` 0: pgrid - cent,
+        1: (pgrid - cent) / (1 + cent))"""
+        check(self.lib.fz_recentre_rows(self.h, ptr(pdfs), int(n), len(pgrid), ptr(pgrid), ptr(cent), int(disp), len(dgrid),
+                                        ptr(dgrid), ptr(out)))
+
+    def cdf_draws(self, pdfs, n, grid, mc, weights=None, edges=None, draws=None, hist=None):
+        """fz_cdf_draws: the CDF draws of ``mc`` (n, Nmc) into ``draws`` and / or their weighted histogram over ``edges``"""
+        check(self.lib.fz_cdf_draws(self.h, ptr(pdfs), int(n), len(grid), ptr(grid), ptr(mc), int(mc.shape[1]), ptr(weights),
+                                    ptr(edges), 0 if edges is None else len(edges) - 1, ptr(draws), ptr(hist)))
+
     # -- the n(z) samplers (samplers.py; fz_nzmc.h) ---------------------------
     def device_empty(self, shape, dtype=np.float64):
         """an uninitialised array in this engine's device memory that lives until its last reference dies (``DeviceArray``)"""

@@ -429,6 +429,31 @@ int  fz_nz_pair_eval(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, doub
 int  fz_nz_sweep(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const double* nz, const double* u, int32_t use_philox,
                  uint32_t key0, uint32_t key1, uint64_t sweep, int64_t* counts);
 
+/* ---- validation of a PDF stack against known values (the arithmetic of plotting.py; docs/diagnostics.md) ----
+ * fz_stack2d -- plotting.input_vs_pdf / input_vs_dpdf (plotting.py:127-159, 309-344): stack (Gx, Gy) = sum over the nsel selected
+ * objects of  kern_e[x - (c - w)] q[y] w_eff / sum(kern on the grid) / sum(q[keep]),  Gx and the kernels being those of the
+ * dictionary last uploaded (fz_kdedict_upload).  pdfs (Nrows, Gy) lives in host or device memory (host rows are staged in chunks).
+ * The per-object arrays are HOST arrays of nsel entries in ascending order of cent: rows (the object's row of pdfs), cent (grid
+ * index of its centre), eidx (its dictionary entry), weff (its weight).  prepared == 0: keep = p > max(p) * pdf_thresh (strict),
+ * q = p / sum(p[keep]) (pdf_thresh = -inf keeps everything); prepared != 0: the rows are already cut and divided, every entry
+ * counts as it stands.  A row without mass adds nothing.  full_range != 0: every x tile visits every object (measurements only).
+ * accumulate != 0: the result is added to what stack holds.  No floating-point atomics: two calls give the same bits.
+ * Refused with the row in the message (-4): a malformed dictionary entry (taps != 2 w + 1), a window [c - w, c + w] that does
+ * not meet [0, Gx), a value of a selected row that is not finite. */
+int  fz_stack2d(fz_ctx* ctx, const double* pdfs, int64_t Nrows, int64_t Gy, int64_t nsel, const int64_t* rows,
+                const int64_t* cent, const int64_t* eidx, const double* weff, double pdf_thresh, int32_t prepared,
+                int32_t full_range, int32_t accumulate, double* stack);
+/* plotting.py:319-320: out (N, Gd) row i = np.interp(dgrid, xp, pdfs[i]) with xp = pgrid - cent[i] (disp 0) or
+ * (pgrid - cent[i]) / (1 + cent[i]) (disp 1); beyond the ends of xp the end values. */
+int  fz_recentre_rows(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const double* pgrid, const double* cent,
+                      int32_t disp, int64_t Gd, const double* dgrid, double* out);
+/* plotting.py:427-436, 501-505: per object cdf = cumsum(pdfs[i]) / cumsum(pdfs[i])[-1]; draws (N, Nmc) =
+ * np.interp(mc[i], grid, cdf) for the caller's Monte-Carlo truths mc (N, Nmc); hist (Nbins) = the draws' histogram over
+ * edges (Nbins + 1, ascending), draw (i, m) weighing weights[i]: bin j holds edges[j] <= u < edges[j + 1], the last bin closed
+ * (np.histogram), summed in a fixed order.  draws or hist may be NULL (then weights / edges are not read).  2 <= G <= 19200. */
+int  fz_cdf_draws(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const double* grid, const double* mc, int64_t Nmc,
+                  const double* weights, const double* edges, int64_t Nbins, double* draws, double* hist);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
