@@ -11,9 +11,9 @@ from .pdf import (PDFDict, gaussian, gauss_kde, gauss_kde_dict, loglike, logprob
                   logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize)
 from .bruteforce import BruteForce
 from .knn import NearestNeighbors
-from . import fitting, networks, pdf, plotting, priors, samplers
+from . import fitting, networks, pdf, plotting, priors, reddening, samplers, simulate
 
 __version__ = "0.1.0"
 __all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gauss_kde",
            "gauss_kde_dict", "loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "luptitude", "magnitude",
-           "pdfs_resample", "pdfs_summarize", "fitting", "networks", "pdf", "plotting", "priors", "samplers"]
+           "pdfs_resample", "pdfs_summarize", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]

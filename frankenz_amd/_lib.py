@@ -124,6 +124,8 @@ ABI = {
     "fz_stack2d": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _F64, _I32, _I32, _I32, _P]),
     "fz_recentre_rows": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I64, _P, _P]),
     "fz_cdf_draws": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
+    "fz_synphot_upload": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "fz_synphot": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _P]),
     "fz_prior_rows_from_grid": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
 }
 

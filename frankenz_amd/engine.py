@@ -420,6 +420,22 @@ class Engine(object):
         check(self.lib.fz_cdf_draws(self.h, ptr(pdfs), int(n), len(grid), ptr(grid), ptr(mc), int(mc.shape[1]), ptr(weights),
                                     ptr(edges), 0 if edges is None else len(edges) - 1, ptr(draws), ptr(hist)))
 
+    # -- synthetic photometry (simulate.py; fz_synphot.h) -----------------------
+    def synphot_upload(self, tb):
+        """fz_synphot_upload of the tables ``tb`` (``simulate._Tables``); what the device already holds is not sent again"""
+        key = _digest(tb.foff, tb.fwave, tb.flw, tb.fwt, tb.ftab, tb.toff, tb.tlw, tb.tas)
+        if key == getattr(self, "_synphot_key", None):
+            return
+        self._synphot_key = None
+        check(self.lib.fz_synphot_upload(self.h, tb.Nf, ptr(tb.foff), ptr(tb.fwave), ptr(tb.flw), ptr(tb.fwt), ptr(tb.ftab),
+                                         tb.Nt, ptr(tb.toff), ptr(tb.tlw), ptr(tb.tas)))
+        self._synphot_key = key
+
+    def synphot(self, tmpl, z, ln1pz, igm, out):
+        """fz_synphot: ``out`` (len(tmpl), Nf), host or device, of the (template, redshift) pairs; ``tmpl`` int64, ``z`` and
+        ``ln1pz`` = log(1 + z) float64 host arrays; ``igm`` 0 none, 1 Madau"""
+        check(self.lib.fz_synphot(self.h, len(tmpl), ptr(tmpl), ptr(z), ptr(ln1pz), int(igm), ptr(out)))
+
     # -- the n(z) samplers (samplers.py; fz_nzmc.h) ---------------------------
     def device_empty(self, shape, dtype=np.float64):
         """an uninitialised array in this engine's device memory that lives until its last reference dies (``DeviceArray``)"""

@@ -454,6 +454,23 @@ int  fz_recentre_rows(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, con
 int  fz_cdf_draws(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const double* grid, const double* mc, int64_t Nmc,
                   const double* weights, const double* edges, int64_t Nbins, double* draws, double* hist);
 
+/* ---- synthetic photometry (simulate.py:811-840, 986-1014 with the Madau IGM of reddening.py:23-95; docs/simulate.md) ----
+ * fz_synphot_upload -- the filter curves and templates of a survey, once.  HOST arrays.  Filters: foff (Nf + 1) offsets into the
+ * concatenated per-point arrays fwave (the wavelength as the reference forms it, exp(log(wavelength))), flw (ln wavelength), fwt (the
+ * trapezoid weight of the point over frequency, transmission / nu included, divided by the filter's norm) and ftab (points, 18):
+ * columns 0..11 the running sums P[j] of the first j Lyman-line terms coeff_i (wave / l_i)^3.46 in the reference's order (P[0] = 0),
+ * columns 12..17 (wave / 912)^{3, 0.46, 1.5, 0.18, -1.32, 1.68}.  Templates: toff (Nt + 1) offsets into tlw (ln wavelength) and
+ * tasinh (arcsinh of f_nu).  Refused (-4): a filter or template of fewer than 2 points, a wavelength that is not positive and
+ * finite, template wavelengths that decrease (repeated filter wavelengths are allowed).
+ * fz_synphot -- out (Npair, Nf)[p][f] = sum_k fwt_k sinh(np.interp(flw_k - ln1pz_p, tlw, tasinh)) exp(-tau(fwave_k, z_p)) over the
+ * points k of filter f and the template tmpl[p]; igm 0: tau = 0, 1: Madau (tau1 + max(tau2, 0), strict wave < l (1 + z)).  tmpl, z
+ * and ln1pz = log(1 + z) are HOST arrays of Npair entries; out lives in host or device memory.  One wave per (pair, filter) and a
+ * fixed-order reduction, no floating-point atomics: two calls give the same bits, and a pair's result does not depend on the other
+ * pairs of the call.  Refused before anything is written: a template index out of range (-3), 1 + z negative or not finite (-4). */
+int  fz_synphot_upload(fz_ctx* ctx, int64_t Nf, const int64_t* foff, const double* fwave, const double* flw, const double* fwt,
+                       const double* ftab, int64_t Nt, const int64_t* toff, const double* tlw, const double* tasinh);
+int  fz_synphot(fz_ctx* ctx, int64_t Npair, const int64_t* tmpl, const double* z, const double* ln1pz, int32_t igm, double* out);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
