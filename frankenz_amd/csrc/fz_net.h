@@ -7,20 +7,24 @@
 namespace fz {
 
 // Which nodes an object's ln-probabilities select, in the reference's order:
-//   use_wt: lnprob > ln(wt_thresh) + max(lnprob), strict (networks.py:887-889), node index ascending (a boolean mask);
+//   use_wt: lnprob > ln(wt_thresh) + max(lnprob), strict (networks.py:887-889), node index ascending (a boolean mask).  wt_thresh = 0
+//           is numpy's: the threshold is -inf, the strict > drops -inf entries.  wt_thresh < 0 (the -inf Network substitutes when both
+//           thresholds are None) keeps EVERY node, -inf entries included (docs/deviations.md: numpy's log gives nan there).
 //   else:   the CDF rule (networks.py:892-895): nodes by ascending ln-prob (ties by index), the prefix whose running probability
 //           exp(l - logsumexp) stays <= 1 - cdf_thresh.  The order is found by rank counting (Nn^2 / 64 compares per wave: this rule
 //           is the rare one), the running sum is a wave scan -- it rounds differently from numpy's sequential cumsum, which can move
-//           a node only if its cdf lies within rounding of the threshold.
+//           a node only if its cdf lies within rounding of the threshold.  As in numpy, a row of nothing but -inf selects nothing
+//           (-inf - -inf = nan), and a row holding +inf selects the entries below +inf (probability 0 each, then nan).
 // Outputs: nsel[i], sel[i][0 .. nsel) (column indices), rawlen[i] = summed length of the selected nodes' lists, and max / logsumexp
 // over the SELECTED entries (networks.py:330-333).  A row holding a nan selects nothing (numpy: every comparison false).
+// One wave per object, blockDim.x / 64 objects per block: the host sizes the block so that the rows fit in LDS.
 __global__ __launch_bounds__(256) void k_net_select(const double* __restrict__ lnprob, int64_t N, int Nn, int use_wt, double wt_thresh,
                                                     double cdf_thresh, const int32_t* __restrict__ match, const int64_t* __restrict__ csr_off,
                                                     int32_t* __restrict__ nsel, int32_t* __restrict__ sel, int64_t* __restrict__ rawlen,
                                                     double* __restrict__ lmap, double* __restrict__ levid) {
     extern __shared__ double s_net[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (i >= N) return;
     double* l = s_net + (size_t)wave * 2 * Nn;                  // the row
     int32_t* ord = reinterpret_cast<int32_t*>(l + Nn);          // CDF rule: column by rank | its probability (as two int words) -- 2 Nn ints
@@ -34,21 +38,23 @@ __global__ __launch_bounds__(256) void k_net_select(const double* __restrict__ l
     int n = 0;
     if (anynan) { n = 0; }
     else if (use_wt) {
-        const double thr = (wt_thresh > 0.0) ? log(wt_thresh) + mx : -INFINITY;      // wt_thresh = -inf / 0: no clipping
+        const double thr = ((wt_thresh > 0.0) ? log(wt_thresh) : -INFINITY) + mx;    // wt_thresh = 0: ln 0 = -inf, as numpy (nan if mx = +inf)
         for (int c0 = 0; c0 < Nn; c0 += 64) {
             const int c = c0 + lane;
-            const bool keep = c < Nn && ((wt_thresh > 0.0) ? (l[c] > thr) : true);
+            const bool keep = c < Nn && ((wt_thresh >= 0.0) ? (l[c] > thr) : true);      // wt_thresh < 0: no clipping
             const unsigned long long m = __ballot(keep);
             const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
             if (keep) so[n + pre] = c;
             n += __builtin_popcountll(m);
         }
-    } else {
-        // logsumexp over the whole row
+    } else if (mx == -INFINITY) { n = 0; }                           // every probability is nan in numpy: no cdf <= the limit
+    else {
+        // logsumexp over the whole row (a row holding +inf: +inf, every finite entry's probability 0, the +inf entries' nan)
+        const bool top = mx == INFINITY;
         double se = 0.0;
-        for (int c = lane; c < Nn; c += 64) se += (mx == -INFINITY) ? 0.0 : exp_neg(l[c] - mx, tb);
+        for (int c = lane; c < Nn; c += 64) se += top ? 0.0 : exp_neg(l[c] - mx, tb);
         se = wave_sum(se);
-        const double lse = mx + log_pos(se, tb);
+        const double lse = top ? mx : mx + log_pos(se, tb);
         // rank of every column in ascending (ln-prob, index) order
         for (int c = lane; c < Nn; c += 64) {
             const double v = l[c];
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(256) void k_net_select(const double* __restrict__ l
         for (int r0 = 0; r0 < Nn && open; r0 += 64) {
             const int r = r0 + lane;
             const int c = r < Nn ? ord[r] : 0;
-            double p = r < Nn ? ((l[c] == -INFINITY) ? 0.0 : exp_neg(l[c] - lse, tb)) : 0.0;
+            double p = r < Nn ? ((l[c] == -INFINITY) ? 0.0 : top ? ((l[c] == INFINITY) ? NAN : 0.0) : exp_neg(l[c] - lse, tb)) : 0.0;
             // inclusive scan over the wave
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) { const double q = __shfl_up(p, o, 64); if (lane >= o) p += q; }
@@ -84,15 +90,16 @@ __global__ __launch_bounds__(256) void k_net_select(const double* __restrict__ l
         if (csr_off) { const int nd = match ? match[c] : c; len += (long long)(csr_off[nd + 1] - csr_off[nd]); }
     }
     smx = wave_max(smx);
+    const bool sfin = smx > -INFINITY && smx < INFINITY;
     double sse = 0.0;
-    for (int s = lane; s < n; s += 64) sse += (smx == -INFINITY) ? 0.0 : exp_neg(l[so[s]] - smx, tb);
+    for (int s = lane; s < n; s += 64) sse += sfin ? exp_neg(l[so[s]] - smx, tb) : 0.0;
     sse = wave_sum(sse);
     len = (long long)wave_sum((double)len);
     if (lane == 0) {
         nsel[i] = n;
         if (rawlen) rawlen[i] = len;
         if (lmap) lmap[i] = smx;                                       // (no entry: -inf, as max over nothing would be undefined)
-        if (levid) levid[i] = (n > 0) ? smx + log_pos(sse, tb) : -INFINITY;
+        if (levid) levid[i] = sfin ? smx + log_pos(sse, tb) : smx;          // (max -inf or +inf: so is the logsumexp)
     }
 }
 

@@ -43,7 +43,7 @@ extern "C" int fz_net_select(fz_ctx* c, const double* lnprob, int64_t N, int32_t
                              double* lmap, double* levid) {
     if (!c || !lnprob || !nsel || !sel) return fail(-1, "fz_net_select: NULL argument");
     if (N <= 0) return 0;
-    if (Nn <= 0 || Nn > 4096) return fail(-5, "fz_net_select: %d nodes unsupported (1..4096: an object's row of node ln-probabilities sits in LDS)", Nn);
+    if (Nn <= 0 || Nn > 4096) return fail(-5, "fz_net_select: %d nodes unsupported (limit: 1..4096 matched nodes, an object's row of node ln-probabilities sits in LDS)", Nn);
     if (!use_wt && !(cdf_thresh > 0.0 && cdf_thresh < 1.0)) return fail(-4, "cdf_thresh must lie in (0, 1)");
     if (rawlen && !csr_off) return fail(-1, "fz_net_select: rawlen needs the node lists' offsets");
     HIPCHK(hipSetDevice(c->device));
@@ -54,11 +54,14 @@ extern "C" int fz_net_select(fz_ctx* c, const double* lnprob, int64_t N, int32_t
     FZCHK(st.in(csr_off, csr_off ? (size_t)(Nnodes + 1) * 8 : 0, &d_off));
     FZCHK(st.out(nsel, (size_t)N * 4, &d_nsel)); FZCHK(st.out(sel, (size_t)N * Nn * 4, &d_sel)); FZCHK(st.out(rawlen, (size_t)N * 8, &d_raw));
     FZCHK(st.out(lmap, (size_t)N * 8, &d_lm)); FZCHK(st.out(levid, (size_t)N * 8, &d_le));
-    const size_t lds = (size_t)4 * 2 * Nn * 8;
+    // a wave per object, 16 Nn bytes of LDS each (the row, and the CDF rule's order): four waves a block up to 2 560 nodes (160 KB),
+    // two up to 4 096 (128 KB)
+    const int waves = Nn <= 2560 ? 4 : 2;
+    const size_t lds = (size_t)waves * 2 * Nn * 8;
     HIPCHK(hipFuncSetAttribute((const void*)fz::k_net_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-        hipLaunchKernelGGL(fz::k_net_select, dim3((unsigned)((N + 3) / 4)), dim3(256), lds, c->stream, (const double*)d_lp, N, (int)Nn, (int)use_wt,
+        hipLaunchKernelGGL(fz::k_net_select, dim3((unsigned)((N + waves - 1) / waves)), dim3(64 * waves), lds, c->stream, (const double*)d_lp, N, (int)Nn, (int)use_wt,
                            wt_thresh, cdf_thresh, (const int32_t*)d_match, (const int64_t*)d_off, (int32_t*)d_nsel, (int32_t*)d_sel, (int64_t*)d_raw,
                            (double*)d_lm, (double*)d_le);
     }

@@ -28,6 +28,8 @@ __all__ = ["populate_network", "Network", "SelfOrganizingMap", "GrowingNeuralGas
            "neighbor_gauss", "neighbor_lorentz"]
 
 _NET_CHUNK = 1 << 16          # objects per device call
+_NODES_MAX = 4096             # matched nodes fz_net_select takes (an object's row sits in LDS)
+_UNION_MAX = 4096             # entries of an object's union table before de-duplication (FZ_KNN_WMAX)
 
 
 class NetworkMap(object):
@@ -324,6 +326,12 @@ class Network(object):
                 nres = [np.ascontiguousarray(np.array([r[k] for r in rows])) for k in range(len(rows[0]))]
                 lnp = np.ascontiguousarray(nres[2], dtype=np.float64)
             nsel, sel, rawlen, _, _ = _select(eng, lnp, wt_thresh, cdf_thresh, match32, None if nodes_only else off)
+            if not nsel.all():
+                # (the reference fails here too, in np.max of nothing; a padded table would quietly fit model 0: docs/deviations.md)
+                k = int(np.argmin(nsel != 0))
+                raise ValueError("object %d selects no node of the network (%d of %d objects in this call do): its node ln-probabilities "
+                                 "hold a nan, or none passes the threshold (wt_thresh=%r, cdf_thresh=%r)"
+                                 % (i0 + k, int((nsel == 0).sum()), n, wt_thresh, cdf_thresh))
             if nodes_only:
                 W = max(int(nsel.max()), 1)
                 res = []
@@ -343,6 +351,13 @@ class Network(object):
                     eng.net_stack(lnp, nsel, sel, match32, node_pdfs, pdfs, lmap, levid)
             else:
                 W = max(int(rawlen.max()), 1)
+                if not rawlen.all():
+                    # (`discrete`: a matched node need not be any model's best one; the reference fails in np.max of nothing)
+                    raise ValueError("object %d: the nodes it selects list no model" % (i0 + int(np.argmin(rawlen != 0))))
+                if W > _UNION_MAX:
+                    raise NotImplementedError("object %d: its selected nodes list %d models before repeats are removed; the union table "
+                                              "of fz_knn_fit_predict holds at most %d (this is not the limit of %d matched nodes)"
+                                              % (i0 + int(np.argmax(rawlen)), W, _UNION_MAX, _NODES_MAX))
                 idx = np.empty((n, W), dtype=np.int64)
                 eng.net_table(nsel, sel, match32, off, items, W, idx)
                 nb = np.empty((n, W), dtype=np.int64); nn_ = np.empty(n, dtype=np.int64)

@@ -322,18 +322,24 @@ int  fz_nz_assign(fz_ctx* ctx, const double* pdfs, int64_t N, int64_t G, const d
  * (networks.py:305-307, 874-876).  Every array may live in host or device memory.
  *
  * fz_net_select -- which nodes an object's (N, Nn) ln-probabilities select, in the reference's order (networks.py:885-896, 316-327):
- *   use_wt != 0: lnprob > ln(wt_thresh) + max(lnprob), strict, node index ascending (wt_thresh <= 0 or -inf: every node);
- *   use_wt == 0: ascending ln-prob, the prefix whose running probability exp(l - logsumexp) stays <= 1 - cdf_thresh.
+ *   use_wt != 0: lnprob > ln(wt_thresh) + max(lnprob), strict, node index ascending.  wt_thresh == 0 is numpy's ln 0 = -inf: every
+ *                node above -inf.  wt_thresh < 0 (the -inf a caller passes for "no threshold at all"): every node, -inf entries too.
+ *   use_wt == 0: ascending ln-prob (ties by index), the prefix whose running probability exp(l - logsumexp) stays <= 1 - cdf_thresh.
+ *   Special rows follow numpy: a row holding a nan selects nothing under either rule; under the CDF rule a row of nothing but -inf
+ *   selects nothing and a row holding +inf selects its entries below +inf; under the weight rule a row holding +inf selects nothing
+ *   (wt_thresh >= 0).  No node selected: nsel 0, rawlen 0, lmap = levid = -inf.
  *   match (Nn, or NULL = identity): the node behind column c (networks.py:873 match_sel); csr_off (Nnodes + 1, or NULL): offsets of
  *   the per-node lists.  Out: nsel (N) int32, sel (N, Nn) int32 column indices (first nsel[i] valid), rawlen (N) int64 summed
  *   list length of the selected nodes (NULL if not wanted), lmap / levid (N): max and logsumexp over the selected entries
- *   (networks.py:330-333; NULL if not wanted).  Nn <= 4096. */
+ *   (networks.py:330-333; NULL if not wanted).  1 <= Nn <= 4096, refused beyond with the limit in the message (a wave per object,
+ *   its row in LDS: four objects per block up to 2 560 nodes, two up to 4 096). */
 int  fz_net_select(fz_ctx* ctx, const double* lnprob, int64_t N, int32_t Nn, int32_t use_wt, double wt_thresh,
                    double cdf_thresh, const int32_t* match, const int64_t* csr_off, int64_t Nnodes, int32_t* nsel,
                    int32_t* sel, int64_t* rawlen, double* lmap, double* levid);
 /* networks.py:912-918: idx (N, W) = the lists (csr_items, int64 model indices) of every object's selected nodes concatenated in
  * order, padded to W with the row's first entry -- the table fz_knn_fit_predict takes: it removes repeats in first-appearance
- * order, which is pandas.unique (networks.py:919), and fits the remaining models (networks.py:925-928). */
+ * order, which is pandas.unique (networks.py:919), and fits the remaining models (networks.py:925-928).  A row longer than W is cut
+ * at W; a row of no entry at all (nsel 0, or only empty lists) is W times index 0: the caller must not fit it. */
 int  fz_net_table(fz_ctx* ctx, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, const int32_t* match,
                   const int64_t* csr_off, const int64_t* csr_items, int64_t Nnodes, int64_t W, int64_t* idx);
 /* networks.py:907-909 (nodes_only): out (N, W) 8-byte elements = plane (N, Nn) at the selected columns, `pad_bits` beyond nsel. */

@@ -1,8 +1,11 @@
 """Inference through a trained network: frankenz_amd.networks.Network against golden G14, generated from the reference's
 _Network with hand-set nodes (networks.py:244-356, 413-560, 782-936, 938-1128, 1130-1473), and against the oracle on a larger case."""
+import functools
+
 import numpy as np
 import pytest
 
+import _net_ref as nr
 import frankenz_oracle as fo
 from conftest import load_golden
 
@@ -147,3 +150,102 @@ def test_a_larger_network_against_the_oracle():
         np.testing.assert_array_equal(net.Nneighbors, [len(v) for v in lists['neighbors']])
         np.testing.assert_array_equal(cat(net.neighbors, 'int'), np.concatenate(lists['neighbors']))
         eq(lm, rlm); eq(le, rle); eq(p, rp, rtol=1e-8, atol=1e-14)
+
+
+# ---- more than one wave's worth of matched nodes, both rules (the kernels themselves: tests/test_hip_net_kernels.py) -----------------
+LPNET = {'free_scale': True, 'ignore_model_err': True, 'return_scale': True}
+RULES = {'wt': dict(), 'cdf': dict(wt_thresh=None, cdf_thresh=0.05)}
+
+
+@functools.lru_cache(maxsize=None)
+def multiwave_case():
+    """1 500 models on 150 nodes, 100 objects"""
+    rs = np.random.RandomState(21)
+    M, N, Nn, B = 1500, 100, 150, 5
+    sig = np.array([0.873, 0.348, 0.418, 0.873, 3.476])
+    Y = rs.lognormal(1., 1., size=(M, 1)) * rs.lognormal(0., .4, size=(M, B)) * 5; Ye = 0.05 * Y; Ym = np.ones((M, B))
+    nodes = Y[rs.choice(M, Nn, replace=False)] * rs.lognormal(0, 0.05, size=(Nn, B))
+    X = Y[rs.choice(M, N)] * rs.lognormal(0, .3, N)[:, None] + sig * rs.randn(N, B); Xe = np.tile(sig, (N, 1)); Xm = np.ones((N, B))
+    z = rs.uniform(0, 6, M); ze = np.full(M, 0.05)
+    return Y, Ye, Ym, nodes, X, Xe, Xm, z, ze
+
+
+@functools.lru_cache(maxsize=None)
+def multiwave_oracle(rule):
+    Y, Ye, Ym, nodes, X, Xe, Xm, z, ze = multiwave_case()
+    onet = fo.populate_network(nodes, Y.copy(), Ye.copy(), Ym.copy(), **RULES[rule])
+    if rule == 'cdf':
+        # the precondition of comparing selections under the CDF rule: no model's and no object's running probability lies within 1e-9
+        # of 1 - cdf_thresh (the device's scan rounds differently from np.cumsum).  Every row, none left out.
+        y = nodes; ym = np.ones_like(y, dtype='bool')
+        gaps = [nr.select(fo.logprob(x, xe, xm, y, np.zeros_like(y), ym, **LPNET)[2], False, 0.0, 0.05)[1]
+                for x, xe, xm in zip(Y.copy(), Ye.copy(), Ym.copy())]
+        y = nodes[np.asarray(onet['Nmatch']) > 0]; ym = np.ones_like(y, dtype='bool')
+        gaps += [nr.select(fo.logprob(x, xe, xm, y, np.zeros_like(y), ym, **LPNET)[2], False, 0.0, 0.05)[1]
+                 for x, xe, xm in zip(X.copy(), Xe.copy(), Xm.copy())]
+        assert len(gaps) == len(Y) + len(X) and min(gaps) > 1e-9, min(gaps)
+    return onet
+
+
+@pytest.mark.parametrize('rule', ['wt', 'cdf'])
+def test_multiwave_populate_network(rule):
+    from frankenz_amd.networks import Network
+    Y, Ye, Ym, nodes, X, Xe, Xm, z, ze = multiwave_case()
+    onet = multiwave_oracle(rule)
+    net = Network(Y.copy(), Ye.copy(), Ym.copy()); net.set_nodes(nodes); net.populate_network(verbose=False, **RULES[rule])
+    np.testing.assert_array_equal(net.nodes_Nmatch, onet['Nmatch'])
+    assert (net.nodes_Nmatch > 0).sum() > 128                  # the objects' rows are longer than two 64-column chunks
+    for a, b in zip(net.nodes_idxs, onet['idxs']):
+        np.testing.assert_array_equal(np.asarray(a, dtype='int'), np.asarray(b, dtype='int'))
+    for a, b in zip(net.nodes_bmus, onet['bmus']):
+        np.testing.assert_array_equal(np.asarray(a, dtype='int'), np.asarray(b, dtype='int'))
+    eq(net.models_lmap, onet['lmap']); eq(net.models_levid, onet['levid'])
+    eq(cat(net.nodes_logwts, 'float'), cat(onet['logwts'], 'float'))
+
+
+@pytest.mark.parametrize('rule', ['wt', 'cdf'])
+@pytest.mark.parametrize('nodes_only', [0, 1])
+def test_multiwave_fit_predict(rule, nodes_only):
+    from frankenz_amd.networks import Network
+    d, od = dicts()
+    Y, Ye, Ym, nodes, X, Xe, Xm, z, ze = multiwave_case()
+    onet = multiwave_oracle(rule)
+    net = Network(Y.copy(), Ye.copy(), Ym.copy()); net.set_nodes(nodes); net.populate_network(verbose=False, **RULES[rule])
+    kw = dict(nodes_only=bool(nodes_only), **RULES[rule])
+    if rule == 'cdf' and not nodes_only:
+        # the CDF rule keeps all but the few best nodes: their lists sum to far more than the union table holds, and the message
+        # says that this limit, not the node limit, was hit; the best-matching-unit lists (one node per model) fit
+        with pytest.raises(NotImplementedError, match='union table'):
+            net.fit_predict(X.copy(), Xe.copy(), Xm.copy(), z, ze, label_dict=d, verbose=False, **kw)
+        kw['discrete'] = True
+    with np.errstate(all='ignore'):
+        p, (lm, le) = net.fit_predict(X.copy(), Xe.copy(), Xm.copy(), z, ze, label_dict=d, return_gof=True, verbose=False, **kw)
+        rp, rlm, rle, lists = fo.network_fit_predict(onet, nodes, X.copy(), Xe.copy(), Xm.copy(), Y, Ye, Ym, z, ze, label_dict=od, **kw)
+    np.testing.assert_array_equal(net.Nneighbors, [len(v) for v in lists['neighbors']])
+    np.testing.assert_array_equal(cat(net.neighbors, 'int'), np.concatenate(lists['neighbors']))
+    eq(lm, rlm); eq(le, rle); eq(p, rp, rtol=1e-8, atol=1e-14)
+
+
+def test_an_object_that_selects_no_node_is_refused():
+    """a nan among an object's node ln-probabilities (here from the user's node likelihood) selects no node; the reference then fails
+    in np.max of nothing.  Here the call is refused before any fit, with the object named, instead of fitting a union table padded
+    with model 0 (docs/deviations.md)"""
+    from frankenz_amd import pdf as fpdf
+    g = load_golden('g14_network_inference')
+    d, _ = dicts()
+    X, Xe, Xm = g['data'].copy(), g['data_err'].copy(), g['data_mask'].copy()
+
+    def mine(x, *a, **k):
+        r = [np.array(v) for v in fpdf.logprob(x, *a, **k)]
+        if np.array_equal(x, g['data'][4]):
+            r[2][1] = np.nan
+        return tuple(r)
+    net = make_net(g, lpnet_func=mine)
+    for kw in (dict(), dict(nodes_only=True), dict(wt_thresh=None, cdf_thresh=0.05)):
+        with pytest.raises(ValueError, match=r'object 4 selects no node .*\(1 of %d objects' % len(X)):
+            net.fit_predict(X.copy(), Xe.copy(), Xm.copy(), g['labels'], g['label_errs'], label_dict=d, verbose=False, **kw)
+        with pytest.raises(ValueError, match='object 4 selects no node'):
+            net.fit(X.copy(), Xe.copy(), Xm.copy(), verbose=False, **kw)
+    net = make_net(g)
+    with pytest.raises(ValueError, match=r'object 0 selects no node .*\(%d of %d objects' % (len(X), len(X))):
+        net.fit(X.copy(), Xe.copy(), Xm.copy(), wt_thresh=1.0, verbose=False)               # strict > against the max: no node
