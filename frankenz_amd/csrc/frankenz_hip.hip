@@ -4,6 +4,7 @@
 // are instantiated per band count in fz_inst.hip.
 #include <mutex>
 #include "fz_ctx.h"
+#include "fz_stage.h"
 #include "fz_kernels.h"
 #include "fz_cdf.h"
 #include "fz_knn.h"
@@ -340,10 +341,7 @@ extern "C" int fz_labels_upload_dict(fz_ctx* c, const int64_t* y_idx, const int6
     upload_begins(c);
     const int64_t Mp = fz_padded_models(M);
     std::vector<int64_t> hy(M), hs(M);
-    if (is_device_ptr(y_idx)) {
-        HIPCHK(hipMemcpy(hy.data(), y_idx, M * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hs.data(), y_std_idx, M * 8, hipMemcpyDeviceToHost));
-    } else { memcpy(hy.data(), y_idx, M * 8); memcpy(hs.data(), y_std_idx, M * 8); }
+    FZCHK(host_read(hy.data(), y_idx, M * 8)); FZCHK(host_read(hs.data(), y_std_idx, M * 8));
     std::vector<int32_t> pos(Mp, 0), cls(Mp, 0);
     std::vector<double> nrm(Mp, 1.0);
     // the grid length is the DICTIONARY's: fz_labels_upload_grid leaves its own grid's length in c->G
@@ -826,7 +824,7 @@ struct OmapGuard { fz_ctx* c; ~OmapGuard() { c->omap = nullptr; } };
 struct PriorBind {
     const fz_prior_lerp* pr = nullptr;
     int kind = 0;              // 0 none, 1 one row for all, 2 row i for object i, 3 rows[i] (the interpolated form is always 3)
-    bool tab_dev = false, rows_dev = false, frac_dev = false;
+    StageRows tabv, rowsv, fracv;          // chunk views of the table (kind 2), the row index and the weights
     const double* tab = nullptr;           // device table when it is resident for the whole call
     int64_t chunk_bytes_per_obj = 0;       // staging a chunk needs per object (kind 2 from host memory)
 };
@@ -837,12 +835,14 @@ static int prior_begin(fz_ctx* c, const fz_prior_lerp* pr, int64_t N, int64_t M,
     if (!pr || !pr->table) return 0;
     if (pr->P <= 0 || pr->P >= ((int64_t)1 << 31)) return fail(-4, "ln-prior table: P = %lld rows is out of range", (long long)pr->P);
     if (pr->frac && (!pr->rows || pr->P < 2)) return fail(-4, "interpolated prior: needs a row index and P >= 2 rows (P = %lld)", (long long)pr->P);
-    pb.pr = pr; pb.tab_dev = is_device_ptr(pr->table); pb.rows_dev = is_device_ptr(pr->rows); pb.frac_dev = is_device_ptr(pr->frac);
+    pb.pr = pr;
+    pb.tabv = StageRows(c, pr->table, (size_t)M * 8, c->d_ptab, STAGE_IN);
+    pb.rowsv = StageRows(c, pr->rows, 8, c->d_prows, STAGE_IN); pb.fracv = StageRows(c, pr->frac, 8, c->d_pfrac, STAGE_IN);
     if (pr->rows) pb.kind = 3;
     else if (pr->P == 1) pb.kind = 1;
     else if (pr->P == N) pb.kind = 2;
     else return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
-    if (pb.tab_dev) { pb.tab = pr->table; return 0; }
+    if (pb.tabv.dev) { pb.tab = pr->table; return 0; }
     if (pb.kind == 2) { pb.chunk_bytes_per_obj = M * 8; return 0; }
     const size_t bytes = (size_t)pr->P * M * 8;
     if ((int64_t)bytes > c->ws_limit) return fail(-2, "ln-prior table of %zu bytes exceeds the workspace limit", bytes);
@@ -858,16 +858,10 @@ static int prior_chunk(fz_ctx* c, const PriorBind& pb, int64_t i0, int64_t n, in
     if (pb.kind == 1) { v.tab = pb.tab; v.ident = 0; }
     else if (pb.kind == 2) {
         v.ident = 1;
-        if (pb.tab_dev) v.tab = pb.tab + i0 * M;
-        else { FZCHK(c->d_ptab.ensure((size_t)n * M * 8)); FZCHK(copy_in(c, c->d_ptab.p, pb.pr->table + i0 * M, (size_t)n * M * 8)); v.tab = c->d_ptab.as<double>(); }
+        FZCHK(pb.tabv.at(i0, n, &v.tab));
     } else {
         v.tab = pb.tab;
-        if (pb.rows_dev) v.rows = pb.pr->rows + i0;
-        else { FZCHK(c->d_prows.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_prows.p, pb.pr->rows + i0, (size_t)n * 8)); v.rows = c->d_prows.as<int64_t>(); }
-        if (pb.pr->frac) {
-            if (pb.frac_dev) v.frac = pb.pr->frac + i0;
-            else { FZCHK(c->d_pfrac.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_pfrac.p, pb.pr->frac + i0, (size_t)n * 8)); v.frac = c->d_pfrac.as<double>(); }
-        }
+        FZCHK(pb.rowsv.at(i0, n, &v.rows)); FZCHK(pb.fracv.at(i0, n, &v.frac));
         int ef = 0;
         FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
             if (v.frac) hipLaunchKernelGGL(k_prior_check_lerp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v.rows, v.frac, n, pb.pr->P, d_flags);
@@ -900,13 +894,10 @@ extern "C" int fz_prior_rows_from_grid(fz_ctx* c, const double* base, int64_t P,
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {base, iz, g, t, table}));
     // host inputs are staged in the buffers of the fz_net_* entry points (nothing of theirs is live across calls)
-    const void* src[4] = {base, iz, g, t};
-    const size_t bytes[4] = {(size_t)P * NZ * NT * 8, (size_t)M * 4, (size_t)M * 8, (size_t)M * 4};
+    StageWhole st{c};
     const void* dev[4];
-    for (int k = 0; k < 4; ++k) {
-        if (is_device_ptr(src[k])) { dev[k] = src[k]; continue; }
-        FZCHK(c->d_net[k].ensure(bytes[k])); FZCHK(copy_in(c, c->d_net[k].p, src[k], bytes[k])); dev[k] = c->d_net[k].p;
-    }
+    FZCHK(st.in(base, (size_t)P * NZ * NT * 8, &dev[0])); FZCHK(st.in(iz, (size_t)M * 4, &dev[1]));
+    FZCHK(st.in(g, (size_t)M * 8, &dev[2])); FZCHK(st.in(t, (size_t)M * 4, &dev[3]));
     int ef = 0;
     FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
         hipLaunchKernelGGL(k_prior_grid_check, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)dev[1], (const double*)dev[2],
@@ -1098,7 +1089,8 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
     const int64_t M = c->M, G = c->G;
     if (c->label_mode == 0) return fail(-1, "fz_fit_predict: labels have not been uploaded");
     c->exact_evidence = (o->exact_evidence != 0) || (ko->exact_evidence != 0);
-    const bool pdf_dev = is_device_ptr(pdfs), lm_dev = is_device_ptr(lmap), le_dev = is_device_ptr(levid);
+    const StageRows lmv(c, lmap, 8, c->d_lmap, STAGE_OUT, true), lev(c, levid, 8, c->d_levid, STAGE_OUT, true);   // (the chunks that are not pipelined)
+    const bool pdf_dev = is_device_ptr(pdfs), lm_dev = lmv.dev, le_dev = lev.dev;
     const bool cdf = !ko->use_wt_thresh;          // reference CDF rule: materialise the chunk's ln-like rows
     PriorBind pb; PriorGuard guard{c};
     FZCHK(prior_begin(c, pr, N, M, pb));
@@ -1152,10 +1144,7 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             d_le = (levid && le_dev) ? levid + i0 : c->d_levid.as<double>() + ((levid && !le_dev) ? i0 : 0);
             if (!lmap) { FZCHK(c->d_lmap.ensure((size_t)n * 8)); d_lm = c->d_lmap.as<double>(); }
             if (!levid) { FZCHK(c->d_levid.ensure((size_t)n * 8)); d_le = c->d_levid.as<double>(); }
-        } else {
-        if (lmap && lm_dev) d_lm = lmap + i0; else { FZCHK(c->d_lmap.ensure(n * 8)); d_lm = c->d_lmap.as<double>(); }
-        if (levid && le_dev) d_le = levid + i0; else { FZCHK(c->d_levid.ensure(n * 8)); d_le = c->d_levid.as<double>(); }
-        }
+        } else { FZCHK(lmv.at(i0, n, &d_lm)); FZCHK(lev.at(i0, n, &d_le)); }
         if (mode == 3) {
             c->mc_lnl_only = 1;                               // only the final ln-like plane is needed here
             FZCHK(run_modec(c, var, n, o));
@@ -1186,8 +1175,7 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             continue;
         }
         if (!pdf_dev) FZCHK(copy_out(c, pdfs + i0 * G, d_pdf, (size_t)n * G * 8));
-        if (lmap && !lm_dev) FZCHK(copy_out(c, lmap + i0, d_lm, n * 8));
-        if (levid && !le_dev) FZCHK(copy_out(c, levid + i0, d_le, n * 8));
+        FZCHK(lmv.back(i0, n)); FZCHK(lev.back(i0, n));
     }
     if (pipe) {
         FZCHK(ship_prev());
@@ -1213,31 +1201,24 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
     FZCHK(wait_for_producers(c, {logwt}));
     c->exact_evidence = ko->exact_evidence != 0;
     const int64_t M = c->label_M, G = c->G;
-    const bool in_dev = is_device_ptr(logwt), pdf_dev = is_device_ptr(pdfs), lm_dev = is_device_ptr(lmap), le_dev = is_device_ptr(levid);
+    const StageRows inv(c, logwt, (size_t)M * 8, c->d_pl[0], STAGE_IN), pdv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_OUT);
+    const StageRows lmv(c, lmap, 8, c->d_lmap, STAGE_OUT, true), lev(c, levid, 8, c->d_levid, STAGE_OUT, true);
     const int linear = is_log ? 0 : 1;
-    int64_t nc = in_dev ? N : std::max<int64_t>(1, c->ws_limit / (M * 8));
+    int64_t nc = inv.dev ? N : std::max<int64_t>(1, c->ws_limit / (M * 8));
     nc = std::min<int64_t>(std::min<int64_t>(nc, N), 1 << 18);
     // c->M may be unset when only labels were uploaded (stand-alone KDE); the kernels only need label_M
     const int64_t savedM = c->M; c->M = M;
+    const auto chunk = [&](int64_t i0, int64_t n) -> int {
+        const double* d_in; double* d_pdf; double* d_lm; double* d_le;
+        FZCHK(inv.at(i0, n, &d_in)); FZCHK(pdv.at(i0, n, &d_pdf)); FZCHK(lmv.at(i0, n, &d_lm)); FZCHK(lev.at(i0, n, &d_le));
+        if (!ko->use_wt_thresh) FZCHK(run_cdf(c, n, (int)M, M, d_in, nullptr, nullptr, is_log ? 1 : 0, ko, d_pdf, d_lm, d_le));
+        else FZCHK(fz_launch_plane_predict(c, d_in, n, M, linear, ko, d_lm, d_le, d_pdf));
+        FZCHK(pdv.back(i0, n)); FZCHK(lmv.back(i0, n));
+        if (is_log) FZCHK(lev.back(i0, n));
+        return 0;
+    };
     int rc = 0;
-    for (int64_t i0 = 0; i0 < N && rc == 0; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        const double* d_in;
-        if (in_dev) d_in = logwt + i0 * M;
-        else { if ((rc = c->d_pl[0].ensure((size_t)n * M * 8))) break; if ((rc = copy_in(c, c->d_pl[0].p, logwt + i0 * M, (size_t)n * M * 8))) break; d_in = c->d_pl[0].as<double>(); }
-        double* d_pdf; double* d_lm; double* d_le;
-        if (pdf_dev) d_pdf = pdfs + i0 * G; else { if ((rc = c->d_pdfs.ensure((size_t)n * G * 8))) break; d_pdf = c->d_pdfs.as<double>(); }
-        if (lmap && lm_dev) d_lm = lmap + i0; else { if ((rc = c->d_lmap.ensure(n * 8))) break; d_lm = c->d_lmap.as<double>(); }
-        if (levid && le_dev) d_le = levid + i0; else { if ((rc = c->d_levid.ensure(n * 8))) break; d_le = c->d_levid.as<double>(); }
-        if (!ko->use_wt_thresh) {
-            if ((rc = run_cdf(c, n, (int)M, M, d_in, nullptr, nullptr, is_log ? 1 : 0, ko, d_pdf, d_lm, d_le))) break;
-        } else {
-            if ((rc = fz_launch_plane_predict(c, d_in, n, M, linear, ko, d_lm, d_le, d_pdf))) break;
-        }
-        if (!pdf_dev && (rc = copy_out(c, pdfs + i0 * G, d_pdf, (size_t)n * G * 8))) break;
-        if (lmap && !lm_dev && (rc = copy_out(c, lmap + i0, d_lm, n * 8))) break;
-        if (levid && !le_dev && is_log && (rc = copy_out(c, levid + i0, d_le, n * 8))) break;
-    }
+    for (int64_t i0 = 0; i0 < N && rc == 0; i0 += nc) rc = chunk(i0, std::min(nc, N - i0));
     c->M = savedM;
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -23,7 +23,8 @@ extern "C" int fz_stack2d(fz_ctx* c, const double* pdfs, int64_t Nrows, int64_t 
     }
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, stack}));
-    const bool p_dev = is_device_ptr(pdfs), s_dev = is_device_ptr(stack);
+    const StageRows pv(c, pdfs, (size_t)Gy * 8, c->d_pdfs, STAGE_IN);
+    const bool p_dev = pv.dev, s_dev = is_device_ptr(stack);
     const int ntx = (int)((Gx + FZ_GEMM_BM - 1) / FZ_GEMM_BM), nty = (int)((Gy + FZ_GEMM_BN - 1) / FZ_GEMM_BN);
     const size_t tile_bytes = (size_t)FZ_GEMM_BM * FZ_GEMM_BN * 8;
     double* d_out = stack;
@@ -79,8 +80,8 @@ extern "C" int fz_stack2d(fz_ctx* c, const double* pdfs, int64_t Nrows, int64_t 
         }
         const int ni = (int)items.size();
         if (ns > 0) {
-            const double* dp = pdfs;
-            if (!p_dev) { FZCHK(c->d_pdfs.ensure((size_t)n * Gy * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * Gy, (size_t)n * Gy * 8)); dp = c->d_pdfs.as<double>(); }
+            const double* dp;
+            FZCHK(pv.at(i0, n, &dp));                              // (device rows: one chunk, i0 = 0, and o.row counts from the first row)
             FZCHK(c->d_net[0].ensure((size_t)ns * sizeof(StackObj))); FZCHK(copy_in(c, c->d_net[0].p, objs.data(), (size_t)ns * sizeof(StackObj)));
             FZCHK(c->d_net[1].ensure((size_t)std::max(ni, 1) * sizeof(StackItem))); FZCHK(copy_in(c, c->d_net[1].p, items.data(), (size_t)ni * sizeof(StackItem)));
             FZCHK(c->d_net[3].ensure(8));
@@ -128,7 +129,7 @@ extern "C" int fz_recentre_rows(fz_ctx* c, const double* pdfs, int64_t N, int64_
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, pgrid, cent, dgrid, out}));
-    const bool p_dev = is_device_ptr(pdfs), o_dev = is_device_ptr(out), c_dev = is_device_ptr(cent);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), cv(c, cent, 8, c->d_lmap, STAGE_IN), ov(c, out, (size_t)Gd * 8, c->d_pl[0], STAGE_OUT);
     FZCHK(c->d_sgrid.ensure((size_t)(G + Gd) * 8));
     FZCHK(copy_in(c, c->d_sgrid.p, pgrid, (size_t)G * 8));
     FZCHK(copy_in(c, c->d_sgrid.as<double>() + G, dgrid, (size_t)Gd * 8));
@@ -137,16 +138,14 @@ extern "C" int fz_recentre_rows(fz_ctx* c, const double* pdfs, int64_t N, int64_
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dp; const double* dc; double* dout;
-        if (p_dev) dp = pdfs + i0 * G; else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (c_dev) dc = cent + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_lmap.p, cent + i0, (size_t)n * 8)); dc = c->d_lmap.as<double>(); }
-        if (o_dev) dout = out + i0 * Gd; else { FZCHK(c->d_pl[0].ensure((size_t)n * Gd * 8)); dout = c->d_pl[0].as<double>(); }
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(cv.at(i0, n, &dc)); FZCHK(ov.at(i0, n, &dout));
         {
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
             hipLaunchKernelGGL(k_recentre, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, dp, n, (int)G, c->d_sgrid.as<double>(), dc, (int)disp,
                                (int)Gd, c->d_sgrid.as<double>() + G, dout);
         }
         HIPCHK(hipGetLastError());
-        if (!o_dev) FZCHK(copy_out(c, out + i0 * Gd, dout, (size_t)n * Gd * 8));
+        FZCHK(ov.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -162,12 +161,13 @@ extern "C" int fz_cdf_draws(fz_ctx* c, const double* pdfs, int64_t N, int64_t G,
     if (N <= 0) { if (hist && !is_device_ptr(hist)) std::fill(hist, hist + Nbins, 0.0); return 0; }
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, grid, mc, weights, edges, draws, hist}));
-    const bool p_dev = is_device_ptr(pdfs), m_dev = is_device_ptr(mc), w_dev = is_device_ptr(weights), d_dev = is_device_ptr(draws);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), mv(c, mc, (size_t)Nmc * 8, c->d_pl[0], STAGE_IN);
+    const StageRows dv(c, draws, (size_t)Nmc * 8, c->d_pl[1], STAGE_OUT), wv(c, hist ? weights : nullptr, 8, c->d_lmap, STAGE_IN);
     const int nb = hist ? (int)Nbins : 0;
     FZCHK(c->d_sgrid.ensure((size_t)(G + nb + 1) * 8));
     FZCHK(copy_in(c, c->d_sgrid.p, grid, (size_t)G * 8));
     if (hist) FZCHK(copy_in(c, c->d_sgrid.as<double>() + G, edges, (size_t)(nb + 1) * 8));
-    const int64_t per_obj = (p_dev ? 0 : G * 8) + (m_dev ? 0 : Nmc * 8) + ((draws && !d_dev) ? Nmc * 8 : 0) + 8;
+    const int64_t per_obj = (pv.dev ? 0 : G * 8) + (mv.dev ? 0 : Nmc * 8) + (dv.staged() ? Nmc * 8 : 0) + 8;
     int64_t nc = std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / per_obj, (int64_t)1 << 22));
     nc = std::min(nc, N);
     const int wpb = G <= 4800 ? 4 : (G <= 9600 ? 2 : 1);               // waves per block: one CDF row each in LDS (as k_summarize)
@@ -177,11 +177,8 @@ extern "C" int fz_cdf_draws(fz_ctx* c, const double* pdfs, int64_t N, int64_t G,
     std::vector<double> total(nb, 0.0), chunk(nb);
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
-        const double *dp, *dm, *dw = nullptr; double* dd = nullptr;
-        if (p_dev) dp = pdfs + i0 * G; else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (m_dev) dm = mc + i0 * Nmc; else { FZCHK(c->d_pl[0].ensure((size_t)n * Nmc * 8)); FZCHK(copy_in(c, c->d_pl[0].p, mc + i0 * Nmc, (size_t)n * Nmc * 8)); dm = c->d_pl[0].as<double>(); }
-        if (draws) { if (d_dev) dd = draws + i0 * Nmc; else { FZCHK(c->d_pl[1].ensure((size_t)n * Nmc * 8)); dd = c->d_pl[1].as<double>(); } }
-        if (hist) { if (w_dev) dw = weights + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_lmap.p, weights + i0, (size_t)n * 8)); dw = c->d_lmap.as<double>(); } }
+        const double *dp, *dm, *dw; double* dd;
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(mv.at(i0, n, &dm)); FZCHK(dv.at(i0, n, &dd)); FZCHK(wv.at(i0, n, &dw));
         // a block serves a run of objects, so that the histogram has a few thousand partial rows whatever N
         const int64_t opb = std::max<int64_t>(wpb, (n + (int64_t)4 * c->cu_count - 1) / ((int64_t)4 * c->cu_count));
         const int64_t nblk = (n + opb - 1) / opb, P = nblk * wpb;
@@ -195,16 +192,13 @@ extern "C" int fz_cdf_draws(fz_ctx* c, const double* pdfs, int64_t N, int64_t G,
                 hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, hp + (int64_t)b * P, P, hp + P * nb + b);
         }
         HIPCHK(hipGetLastError());
-        if (draws && !d_dev) FZCHK(copy_out(c, draws + i0 * Nmc, dd, (size_t)n * Nmc * 8));
+        FZCHK(dv.back(i0, n));
         if (hist) {
             FZCHK(copy_out(c, chunk.data(), hp + P * nb, (size_t)nb * 8));
             for (int b = 0; b < nb; ++b) total[b] += chunk[b];
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (hist) {
-        if (is_device_ptr(hist)) HIPCHK(hipMemcpy(hist, total.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
-        else std::copy(total.begin(), total.end(), hist);
-    }
+    if (hist) FZCHK(host_write(hist, total.data(), (size_t)nb * 8));
     return 0;
 }

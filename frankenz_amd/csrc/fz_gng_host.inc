@@ -1,5 +1,5 @@
 // ---- networks.py ABI: training of a growing neural gas (fz_gng.h) ---------------------------------------
-// Every array may live in host or device memory; host arrays are staged through the context's buffers (NetStage, fz_net_host.inc).
+// Every array may live in host or device memory; host arrays are staged through the context's buffers (StageWhole, fz_stage.h).
 namespace {
 // the sizes of the two state arrays (include/frankenz_hip.h gives the layout; networks._gng_state_sizes is the Python twin)
 int64_t gng_state_doubles(int32_t cap, int32_t B) { return 2 * (int64_t)cap * B + cap + 2 * (int64_t)B; }
@@ -35,8 +35,7 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
     // host-side checks that keep every device access in bounds: the drawn rows and the counters of the state
     FZCHK(check_draws("fz_gng_train", draws, s0, s1, M));
     int32_t cnt[GNG_NCNT];
-    if (is_device_ptr(istate)) HIPCHK(hipMemcpy(cnt, istate, sizeof(cnt), hipMemcpyDeviceToHost));
-    else std::memcpy(cnt, istate, sizeof(cnt));
+    FZCHK(host_read(cnt, istate, sizeof(cnt)));
     if (cnt[fz::GNG_NN] < 2 || cnt[fz::GNG_NN] > cap || cnt[fz::GNG_NP] < 0 || cnt[fz::GNG_NP] > prune_cap || cnt[fz::GNG_EC] < 0 ||
         cnt[fz::GNG_EC] > edge_cap || cnt[fz::GNG_STATUS] != 0 || cnt[fz::GNG_AL0] < -1 || cnt[fz::GNG_AL0] >= cap || cnt[fz::GNG_AL1] < -1 ||
         cnt[fz::GNG_AL1] >= cap || (cnt[fz::GNG_CUR] & ~1))
@@ -51,7 +50,7 @@ extern "C" int fz_gng_train(fz_ctx* c, const double* models, const double* model
     const int64_t nb = (T - 1) / nbatch + 1;
     const size_t nf = (size_t)gng_state_doubles(cap, B) * 8, ni = (size_t)gng_state_ints(cap, max_degree, prune_cap, edge_cap) * 4;
 
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_x, *d_xe, *d_xm, *d_dr; void *d_f, *d_i, *d_ids, *d_bmus, *d_batch;
     FZCHK(st.in(models, (size_t)M * B * 8, &d_x)); FZCHK(st.in(models_err, (size_t)M * B * 8, &d_xe));
     FZCHK(st.in(models_mask, (size_t)M * B * 8, &d_xm)); FZCHK(st.in(draws, (size_t)T * 8, &d_dr));

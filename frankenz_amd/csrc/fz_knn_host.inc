@@ -217,15 +217,14 @@ extern "C" int fz_knn_query(fz_ctx* c, const double* q, int64_t N, int32_t k, do
     else return fail(-5, "fz_knn_query: Minkowski p=%g is not implemented (1, 2 and inf are)", lp_norm);
     FZCHK(check_knn_k(c, k, pnorm, "fz_knn_query"));
     const double b2 = (dub == INFINITY || pnorm != 2) ? dub : dub * dub;      // KDTree keeps d < bound (strict)
-    const bool qdev = is_device_ptr(q), idev = is_device_ptr(idx);
+    const StageRows qv(c, q, (size_t)F * 8, c->d_q, STAGE_IN), iv(c, idx, (size_t)K * k * 8, c->d_idx, STAGE_OUT);
     const int64_t nc = std::min<int64_t>(N, 1 << 18);
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dq; int64_t* di;
-        if (qdev) dq = q + i0 * F; else { FZCHK(c->d_q.ensure((size_t)n * F * 8)); FZCHK(copy_in(c, c->d_q.p, q + i0 * F, (size_t)n * F * 8)); dq = c->d_q.as<double>(); }
-        if (idev) di = idx + i0 * K * k; else { FZCHK(c->d_idx.ensure((size_t)n * K * k * 8)); di = c->d_idx.as<int64_t>(); }
+        FZCHK(qv.at(i0, n, &dq)); FZCHK(iv.at(i0, n, &di));
         FZCHK(run_knnquery(c, dq, n, k, b2, di, pnorm));
-        if (!idev) FZCHK(copy_out(c, idx + i0 * K * k, di, (size_t)n * K * k * 8));
+        FZCHK(iv.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -260,18 +259,17 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
     PriorBind pb; PriorGuard guard{c};
     FZCHK(prior_begin(c, pr, N, c->M, pb));
     const bool want_prior = pb.kind || lnprior || lnprob;
-    // outputs: {ptr, bytes per object}
-    struct Out { void* host; size_t per; DevBuf* stage; void* dev; };
+    // outputs: {ptr, bytes per object, the buffer that stages it}
     constexpr int NO = 12;
-    Out outs[NO] = {{neighbors, (size_t)W * 8, &c->d_nbr, nullptr}, {nnbr, 8, &c->d_nn, nullptr},
-                    {lnlike, (size_t)W * 8, &c->d_pl[0], nullptr}, {chi2, (size_t)W * 8, &c->d_pl[1], nullptr},
-                    {ndim, (size_t)W * 8, &c->d_pl[2], nullptr}, {scale, (size_t)W * 8, &c->d_pl[3], nullptr},
-                    {scale_err, (size_t)W * 8, &c->d_pl[4], nullptr}, {pdfs, (size_t)G * 8, &c->d_pdfs, nullptr},
-                    {lmap, 8, &c->d_lmap, nullptr}, {levid, 8, &c->d_levid, nullptr},
-                    {lnprior, (size_t)W * 8, &c->d_pl[5], nullptr}, {lnprob, (size_t)W * 8, &c->d_pl[6], nullptr}};
-    const bool idev = is_device_ptr(idx);
-    size_t per_obj = (size_t)W * 8 * 3 + (size_t)pb.chunk_bytes_per_obj;
-    for (auto& u : outs) if (u.host && !is_device_ptr(u.host)) per_obj += u.per;
+    const size_t row = (size_t)W * 8;
+    const StageRows outs[NO] = {{c, neighbors, row, c->d_nbr, STAGE_OUT}, {c, nnbr, 8, c->d_nn, STAGE_OUT}, {c, lnlike, row, c->d_pl[0], STAGE_OUT},
+                                {c, chi2, row, c->d_pl[1], STAGE_OUT}, {c, ndim, row, c->d_pl[2], STAGE_OUT}, {c, scale, row, c->d_pl[3], STAGE_OUT},
+                                {c, scale_err, row, c->d_pl[4], STAGE_OUT}, {c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_OUT},
+                                {c, lmap, 8, c->d_lmap, STAGE_OUT}, {c, levid, 8, c->d_levid, STAGE_OUT},
+                                {c, lnprior, row, c->d_pl[5], STAGE_OUT}, {c, lnprob, row, c->d_pl[6], STAGE_OUT}};
+    const StageRows iv(c, idx, row, c->d_idx, STAGE_IN);
+    size_t per_obj = row * 3 + (size_t)pb.chunk_bytes_per_obj;
+    for (auto& u : outs) if (u.staged()) per_obj += u.row;
     int64_t nc = std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (int64_t)per_obj, 1 << 18));
     nc = std::min(nc, N);
     const bool cdf = pdfs && !ko->use_wt_thresh;
@@ -285,15 +283,12 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
         FZCHK(prior_chunk(c, pb, i0, n, c->M));
         const int var = pick_var(c, fl);
         const int64_t* di;
-        if (idev) di = idx + i0 * W; else { FZCHK(c->d_idx.ensure((size_t)n * W * 8)); FZCHK(copy_in(c, c->d_idx.p, idx + i0 * W, (size_t)n * W * 8)); di = c->d_idx.as<int64_t>(); }
-        for (auto& u : outs) {
-            if (!u.host) u.dev = nullptr;
-            else if (is_device_ptr(u.host)) u.dev = (char*)u.host + (size_t)i0 * u.per;
-            else { FZCHK(u.stage->ensure((size_t)n * u.per)); u.dev = u.stage->p; }
-        }
-        KnnOut ko_; ko_.neighbors = (int64_t*)outs[0].dev; ko_.nnbr = (int64_t*)outs[1].dev; ko_.lnlike = (double*)outs[2].dev;
-        ko_.chi2 = (double*)outs[3].dev; ko_.ndim = (int64_t*)outs[4].dev; ko_.scale = (double*)outs[5].dev;
-        ko_.serr = (double*)outs[6].dev; ko_.pdfs = (double*)outs[7].dev; ko_.lmap = (double*)outs[8].dev; ko_.levid = (double*)outs[9].dev;
+        FZCHK(iv.at(i0, n, &di));
+        void* dev[NO];
+        for (int u = 0; u < NO; ++u) FZCHK(outs[u].at(i0, n, &dev[u]));
+        KnnOut ko_; ko_.neighbors = (int64_t*)dev[0]; ko_.nnbr = (int64_t*)dev[1]; ko_.lnlike = (double*)dev[2];
+        ko_.chi2 = (double*)dev[3]; ko_.ndim = (int64_t*)dev[4]; ko_.scale = (double*)dev[5];
+        ko_.serr = (double*)dev[6]; ko_.pdfs = (double*)dev[7]; ko_.lmap = (double*)dev[8]; ko_.levid = (double*)dev[9];
         int ef = 0;
         if (!rows_route) {
             FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) { return run_knnsubset(c, mode, var, o->dim_prior, n, di, (int)W, ko, &ko_, d_flags); }));
@@ -330,9 +325,9 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
             if (!ef) {
                 const double* lw = lpl;
                 if (want_prior) {
-                    double* lpr = (double*)outs[11].dev;
+                    double* lpr = (double*)dev[11];
                     if (!lpr) { FZCHK(c->d_pl[6].ensure((size_t)n * W * 8)); lpr = c->d_pl[6].as<double>(); }
-                    FZCHK(prior_add(c, lpl, n, W, nb, nn, (double*)outs[10].dev, lpr));
+                    FZCHK(prior_add(c, lpl, n, W, nb, nn, (double*)dev[10], lpr));
                     lw = lpr;
                 }
                 if (ko_.pdfs) {
@@ -346,8 +341,7 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
         }
         if (ef) return fail(-3, "a neighbour index is outside [0, Nmodel): KDTree returns Nmodel for neighbours beyond "
                                 "distance_upper_bound and the reference then fails on models[idxs] (knn.py:847)");
-        for (auto& u : outs)
-            if (u.host && !is_device_ptr(u.host)) FZCHK(copy_out(c, (char*)u.host + (size_t)i0 * u.per, u.dev, (size_t)n * u.per));
+        for (auto& u : outs) FZCHK(u.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -393,13 +387,13 @@ extern "C" int fz_knn_search_fit_predict_prior_lerp(fz_ctx* c, const double* q, 
     else return fail(-5, "fz_knn_search_fit_predict: Minkowski p=%g is not implemented (1, 2 and inf are)", lp_norm);
     FZCHK(check_knn_k(c, k, pnorm, "fz_knn_search_fit_predict"));
     const double b2 = (dub == INFINITY || pnorm != 2) ? dub : dub * dub;
-    const bool qdev = is_device_ptr(q);
+    const StageRows qv(c, q, (size_t)F * 8, c->d_q, STAGE_IN);
     const int64_t nc = std::min<int64_t>(N, 1 << 17);
     FZCHK(c->d_idxs.ensure((size_t)nc * W * 8));
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dq;
-        if (qdev) dq = q + i0 * F; else { FZCHK(c->d_q.ensure((size_t)n * F * 8)); FZCHK(copy_in(c, c->d_q.p, q + i0 * F, (size_t)n * F * 8)); dq = c->d_q.as<double>(); }
+        FZCHK(qv.at(i0, n, &dq));
         FZCHK(run_knnquery(c, dq, n, k, b2, c->d_idxs.as<int64_t>(), pnorm));
         fz_prior_lerp pc; const fz_prior_lerp* prc = nullptr;
         if (pr && pr->table) {
@@ -429,19 +423,15 @@ extern "C" int fz_knn_predict_logwt(fz_ctx* c, const double* logwt, const int64_
     FZCHK(wait_for_producers(c, {logwt, neighbors, nnbr, pdfs, lmap, levid}));
     const int64_t G = c->G, M = c->label_M;
     const int64_t nc = std::min<int64_t>(N, std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (W * 16 + G * 8), 1 << 18)));
+    const StageRows lv(c, logwt, (size_t)W * 8, c->d_pl[0], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_nbr, STAGE_IN), cv(c, nnbr, 8, c->d_nn, STAGE_IN);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_OUT), mv(c, lmap, 8, c->d_lmap, STAGE_OUT, true), ev(c, levid, 8, c->d_levid, STAGE_OUT, true);
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dl; const int64_t* dn; const int64_t* dc; double *dp, *dm, *de;
-        if (is_device_ptr(logwt)) dl = logwt + i0 * W; else { FZCHK(c->d_pl[0].ensure(n * W * 8)); FZCHK(copy_in(c, c->d_pl[0].p, logwt + i0 * W, n * W * 8)); dl = c->d_pl[0].as<double>(); }
-        if (is_device_ptr(neighbors)) dn = neighbors + i0 * W; else { FZCHK(c->d_nbr.ensure(n * W * 8)); FZCHK(copy_in(c, c->d_nbr.p, neighbors + i0 * W, n * W * 8)); dn = c->d_nbr.as<int64_t>(); }
-        if (is_device_ptr(nnbr)) dc = nnbr + i0; else { FZCHK(c->d_nn.ensure(n * 8)); FZCHK(copy_in(c, c->d_nn.p, nnbr + i0, n * 8)); dc = c->d_nn.as<int64_t>(); }
-        if (is_device_ptr(pdfs)) dp = pdfs + i0 * G; else { FZCHK(c->d_pdfs.ensure(n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (lmap && is_device_ptr(lmap)) dm = lmap + i0; else { FZCHK(c->d_lmap.ensure(n * 8)); dm = c->d_lmap.as<double>(); }
-        if (levid && is_device_ptr(levid)) de = levid + i0; else { FZCHK(c->d_levid.ensure(n * 8)); de = c->d_levid.as<double>(); }
+        FZCHK(lv.at(i0, n, &dl)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc));
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(mv.at(i0, n, &dm)); FZCHK(ev.at(i0, n, &de));
         FZCHK(knn_predict_chunk(c, n, M, dl, dn, dc, (int)W, ko, dp, dm, de));
-        if (!is_device_ptr(pdfs)) FZCHK(copy_out(c, pdfs + i0 * G, dp, n * G * 8));
-        if (lmap && !is_device_ptr(lmap)) FZCHK(copy_out(c, lmap + i0, dm, n * 8));
-        if (levid && !is_device_ptr(levid)) FZCHK(copy_out(c, levid + i0, de, n * 8));
+        FZCHK(pv.back(i0, n)); FZCHK(mv.back(i0, n)); FZCHK(ev.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;

@@ -1,42 +1,5 @@
 // ---- networks.py ABI: inference through a trained network (fz_net.h) --------------------------------
-// Every array may live in host or device memory; host arrays are staged through the context's buffers.
-namespace {
-struct NetStage {
-    fz_ctx* c; int used = 0;
-    // device view of `p` (n bytes): the pointer itself, or a staged copy (in: copied now; out: copied back by finish())
-    struct Out { void* host; void* dev; size_t bytes; };
-    std::vector<Out> outs;
-    int in(const void* p, size_t bytes, const void** dev) {
-        if (!p) { *dev = nullptr; return 0; }
-        if (is_device_ptr(p)) { *dev = p; return 0; }
-        if (used >= 10) return fail(-1, "internal: staging slots exhausted");
-        DevBuf& b = c->d_net[used++];
-        FZCHK(b.ensure(bytes ? bytes : 8));
-        FZCHK(copy_in(c, b.p, p, bytes));
-        *dev = b.p;
-        return 0;
-    }
-    int out(void* p, size_t bytes, void** dev) {
-        if (!p) { *dev = nullptr; return 0; }
-        if (is_device_ptr(p)) { *dev = p; return 0; }
-        if (used >= 10) return fail(-1, "internal: staging slots exhausted");
-        DevBuf& b = c->d_net[used++];
-        FZCHK(b.ensure(bytes ? bytes : 8));
-        *dev = b.p;
-        outs.push_back({p, b.p, bytes});
-        return 0;
-    }
-    // out() whose staged copy starts as the caller's array: in/out arrays, and outputs only part of which is written
-    int inout(void* p, size_t bytes, void** dev) {
-        FZCHK(out(p, bytes, dev));
-        return *dev != p ? copy_in(c, *dev, p, bytes) : 0;
-    }
-    int finish() {
-        for (auto& o : outs) FZCHK(copy_out(c, o.host, o.dev, o.bytes));
-        return 0;
-    }
-};
-}  // namespace
+// Every array may live in host or device memory; host arrays are staged through the context's buffers (StageWhole, fz_stage.h).
 
 extern "C" int fz_net_select(fz_ctx* c, const double* lnprob, int64_t N, int32_t Nn, int32_t use_wt, double wt_thresh, double cdf_thresh,
                              const int32_t* match, const int64_t* csr_off, int64_t Nnodes, int32_t* nsel, int32_t* sel, int64_t* rawlen,
@@ -48,7 +11,7 @@ extern "C" int fz_net_select(fz_ctx* c, const double* lnprob, int64_t N, int32_t
     if (rawlen && !csr_off) return fail(-1, "fz_net_select: rawlen needs the node lists' offsets");
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {lnprob, match, csr_off, nsel, sel, rawlen, lmap, levid}));
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_lp, *d_match, *d_off; void *d_nsel, *d_sel, *d_raw, *d_lm, *d_le;
     FZCHK(st.in(lnprob, (size_t)N * Nn * 8, &d_lp)); FZCHK(st.in(match, (size_t)Nn * 4, &d_match));
     FZCHK(st.in(csr_off, csr_off ? (size_t)(Nnodes + 1) * 8 : 0, &d_off));
@@ -77,14 +40,10 @@ extern "C" int fz_net_table(fz_ctx* c, const int32_t* nsel, const int32_t* sel, 
     if (N <= 0 || W <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {nsel, sel, match, csr_off, csr_items, idx}));
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_nsel, *d_sel, *d_match, *d_off, *d_items; void* d_idx;
     int64_t nitems = 0;
-    {
-        int64_t last = 0;
-        if (is_device_ptr(csr_off)) HIPCHK(hipMemcpy(&last, csr_off + Nnodes, 8, hipMemcpyDeviceToHost)); else last = csr_off[Nnodes];
-        nitems = last;
-    }
+    FZCHK(host_read(&nitems, csr_off + Nnodes, 8));
     FZCHK(st.in(nsel, (size_t)N * 4, &d_nsel)); FZCHK(st.in(sel, (size_t)N * Nn * 4, &d_sel)); FZCHK(st.in(match, (size_t)Nn * 4, &d_match));
     FZCHK(st.in(csr_off, (size_t)(Nnodes + 1) * 8, &d_off)); FZCHK(st.in(csr_items, (size_t)nitems * 8, &d_items));
     FZCHK(st.out(idx, (size_t)N * W * 8, &d_idx));
@@ -105,7 +64,7 @@ extern "C" int fz_net_gather(fz_ctx* c, const void* plane, const int32_t* nsel, 
     if (N <= 0 || W <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {plane, nsel, sel, out}));
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_pl, *d_nsel, *d_sel; void* d_out;
     FZCHK(st.in(plane, (size_t)N * Nn * 8, &d_pl)); FZCHK(st.in(nsel, (size_t)N * 4, &d_nsel)); FZCHK(st.in(sel, (size_t)N * Nn * 4, &d_sel));
     FZCHK(st.out(out, (size_t)N * W * 8, &d_out));
@@ -124,7 +83,7 @@ extern "C" int fz_net_stack(fz_ctx* c, const double* lnprob, const int32_t* nsel
     if (N <= 0 || G <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {lnprob, nsel, sel, match, node_pdfs, pdfs, lmap, levid}));
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_lp, *d_nsel, *d_sel, *d_match, *d_np; void *d_pdf, *d_lm, *d_le;
     FZCHK(st.in(lnprob, (size_t)N * Nn * 8, &d_lp)); FZCHK(st.in(nsel, (size_t)N * 4, &d_nsel)); FZCHK(st.in(sel, (size_t)N * Nn * 4, &d_sel));
     FZCHK(st.in(match, (size_t)Nn * 4, &d_match)); FZCHK(st.in(node_pdfs, (size_t)Nnodes * G * 8, &d_np));

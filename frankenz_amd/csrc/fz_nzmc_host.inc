@@ -1,6 +1,6 @@
 // ---- samplers.py ABI: the n(z) samplers' chains (kernels in fz_nzmc.h; docs/samplers.md) ----------------------
 // The stack (N, G) and the per-object state (overlap, the pair's difference column) are DEVICE arrays of the caller: they stay
-// resident over a whole chain.  The G-sized and table arguments may live in host or device memory (NetStage).
+// resident over a whole chain.  The G-sized and table arguments may live in host or device memory (StageWhole, fz_stage.h).
 namespace {
 // scratch of a chain call: block partials of two sums, and the NzState
 int nz_scratch(fz_ctx* c, int64_t nblk, double** partial, fz::NzState** st) {
@@ -49,17 +49,16 @@ extern "C" int fz_pdfs_colsum(fz_ctx* c, const double* pdfs, int64_t N, int64_t 
     const int64_t nblk = (N + NZ_COLROWS - 1) / NZ_COLROWS;
     FZCHK(c->d_pl[0].ensure((size_t)nblk * G * 8));
     double* part = c->d_pl[0].as<double>();
-    const bool p_dev = is_device_ptr(pdfs);
-    int64_t nc = p_dev ? N : std::max<int64_t>(NZ_COLROWS, std::min<int64_t>(c->ws_limit / (G * 8), (int64_t)1 << 22) / NZ_COLROWS * NZ_COLROWS);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN);
+    int64_t nc = pv.dev ? N : std::max<int64_t>(NZ_COLROWS, std::min<int64_t>(c->ws_limit / (G * 8), (int64_t)1 << 22) / NZ_COLROWS * NZ_COLROWS);
     nc = std::min(nc, N);
-    NetStage st{c};
+    StageWhole st{c};
     void* d_out; FZCHK(st.out(colsum, (size_t)G * 8, &d_out));
     {
         for (int64_t i0 = 0; i0 < N; i0 += nc) {
             const int64_t n = std::min(nc, N - i0);
             const double* dp;
-            if (p_dev) dp = pdfs + i0 * G;
-            else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
+            FZCHK(pv.at(i0, n, &dp));
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
             hipLaunchKernelGGL(fz::k_colsum_part, dim3((unsigned)((n + NZ_COLROWS - 1) / NZ_COLROWS)), dim3(NZ_NT), 0, c->stream, dp, n, (int)G,
                                part + (i0 / NZ_COLROWS) * G);
@@ -88,23 +87,16 @@ extern "C" int fz_nz_pairs(fz_ctx* c, const double* pdfs, int64_t N, int64_t G, 
     // the pairs index the stack's columns on the device: checked here
     {
         std::vector<int64_t> pr((size_t)(p1 - p0) * 2);
-        if (is_device_ptr(pairs)) HIPCHK(hipMemcpy(pr.data(), pairs + 2 * p0, pr.size() * 8, hipMemcpyDeviceToHost));
-        else std::memcpy(pr.data(), pairs + 2 * p0, pr.size() * 8);
+        FZCHK(host_read(pr.data(), pairs + 2 * p0, pr.size() * 8));
         for (int64_t v : pr) if (v < 0 || v >= G) return fail(-3, "fz_nz_pairs: bin %lld of a pair outside [0, %lld)", (long long)v, (long long)G);
     }
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_pairs, *d_nrm, *d_exp; void *d_pos, *d_lnp, *d_smp, *d_slnp, *d_acc, *d_gs;
     FZCHK(st.in(pairs, (size_t)P * 16, &d_pairs)); FZCHK(st.in(normals, (size_t)P * mh_steps * 8, &d_nrm)); FZCHK(st.in(expo, (size_t)P * mh_steps * 8, &d_exp));
-    FZCHK(st.out(pos, (size_t)G * 8, &d_pos)); FZCHK(st.out(lnpost, 8, &d_lnp));
-    FZCHK(st.out(samples, (size_t)nsamp * G * 8, &d_smp)); FZCHK(st.out(samples_lnp, (size_t)nsamp * 8, &d_slnp));
-    FZCHK(st.out(accept, (size_t)P * mh_steps * 4, &d_acc)); FZCHK(st.out(gscale, (size_t)P * 8, &d_gs));
     // in/out and partly written arrays: a staged copy starts from the caller's values
-    if (d_pos != (void*)pos) FZCHK(copy_in(c, d_pos, pos, (size_t)G * 8));
-    if (d_lnp != (void*)lnpost) FZCHK(copy_in(c, d_lnp, lnpost, 8));
-    if (d_smp != (void*)samples) FZCHK(copy_in(c, d_smp, samples, (size_t)nsamp * G * 8));
-    if (d_slnp != (void*)samples_lnp) FZCHK(copy_in(c, d_slnp, samples_lnp, (size_t)nsamp * 8));
-    if (d_acc != (void*)accept) FZCHK(copy_in(c, d_acc, accept, (size_t)P * mh_steps * 4));
-    if (d_gs != (void*)gscale) FZCHK(copy_in(c, d_gs, gscale, (size_t)P * 8));
+    FZCHK(st.inout(pos, (size_t)G * 8, &d_pos)); FZCHK(st.inout(lnpost, 8, &d_lnp));
+    FZCHK(st.inout(samples, (size_t)nsamp * G * 8, &d_smp)); FZCHK(st.inout(samples_lnp, (size_t)nsamp * 8, &d_slnp));
+    FZCHK(st.inout(accept, (size_t)P * mh_steps * 4, &d_acc)); FZCHK(st.inout(gscale, (size_t)P * 8, &d_gs));
     const int64_t nblk = (N + NZ_CHUNK - 1) / NZ_CHUNK;
     double* part; fz::NzState* ns;
     FZCHK(nz_scratch(c, nblk, &part, &ns));
@@ -181,22 +173,19 @@ extern "C" int fz_nz_sweep(fz_ctx* c, const double* pdfs, int64_t N, int64_t G, 
     if (N <= 0 || G <= 0 || G >= ((int64_t)1 << 24)) return fail(-4, "fz_nz_sweep: bad shape");
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, nz, u, counts}));
-    const bool p_dev = is_device_ptr(pdfs), u_dev = is_device_ptr(u), c_dev = is_device_ptr(counts);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), uv(c, use_philox ? nullptr : u, 8, c->d_lmap, STAGE_IN);
+    const bool c_dev = is_device_ptr(counts);
     FZCHK(c->d_sgrid.ensure((size_t)G * 8)); FZCHK(copy_in(c, c->d_sgrid.p, nz, (size_t)G * 8));
     FZCHK(c->d_sloss.ensure((size_t)G * 8));
     HIPCHK(hipMemsetAsync(c->d_sloss.p, 0, (size_t)G * 8, c->stream));
-    int64_t nc = p_dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 32), (int64_t)1 << 22));
+    int64_t nc = pv.dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 32), (int64_t)1 << 22));
     nc = std::min(nc, N);
     const size_t rows_lds = (size_t)4 * G * 8;                  // as fz_nz_assign: four rows of p * nz in LDS up to 48 KB
     const int staged = rows_lds <= 48 * 1024;
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
-        const double* dp; const double* du = nullptr;
-        if (p_dev) dp = pdfs + i0 * G;
-        else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (!use_philox) {
-            if (u_dev) du = u + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_lmap.p, u + i0, (size_t)n * 8)); du = c->d_lmap.as<double>(); }
-        }
+        const double* dp; const double* du;
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(uv.at(i0, n, &du));
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
         const dim3 grid((unsigned)((n + 3) / 4)), blk(256);
         if (use_philox)

@@ -1,5 +1,5 @@
 // ---- networks.py ABI: training of a self-organizing map (fz_som.h) -------------------------------------
-// Every array may live in host or device memory; host arrays are staged through the context's buffers (NetStage, fz_net_host.inc).
+// Every array may live in host or device memory; host arrays are staged through the context's buffers (StageWhole, fz_stage.h).
 extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* models_err, const double* models_mask, int64_t M, int32_t B,
                             double* nodes, const int32_t* nodes_pos, int32_t NNODE, int32_t NPROJ, const int64_t* draws,
                             const double* learn_rate, const double* sigma, int64_t T, int32_t neighbor_kind, int32_t use_wt,
@@ -21,8 +21,7 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
     // host-side checks that keep every device access in bounds: the drawn rows, and the squared-distance range (CDF histogram)
     FZCHK(check_draws("fz_som_train", draws, s0, s1, M));
     std::vector<int32_t> pos((size_t)NNODE * NPROJ);
-    if (is_device_ptr(nodes_pos)) HIPCHK(hipMemcpy(pos.data(), nodes_pos, pos.size() * 4, hipMemcpyDeviceToHost));
-    else std::memcpy(pos.data(), nodes_pos, pos.size() * 4);
+    FZCHK(host_read(pos.data(), nodes_pos, pos.size() * 4));
     double dmax = 0.0;
     for (int p = 0; p < NPROJ; ++p) {
         int32_t lo = pos[p], hi = pos[p];
@@ -40,7 +39,7 @@ extern "C" int fz_som_train(fz_ctx* c, const double* models, const double* model
     const bool lds_nodes = fixed + hist + resident <= lds_max;
     const size_t lds = fixed + hist + (lds_nodes ? resident : 0);
 
-    NetStage st{c};
+    StageWhole st{c};
     const void *d_x, *d_xe, *d_xm, *d_pos, *d_dr, *d_lr, *d_sig; void *d_nodes, *d_bmus;
     FZCHK(st.in(models, (size_t)M * B * 8, &d_x)); FZCHK(st.in(models_err, (size_t)M * B * 8, &d_xe));
     FZCHK(st.in(models_mask, (size_t)M * B * 8, &d_xm)); FZCHK(st.in(nodes_pos, pos.size() * 4, &d_pos));

@@ -8,13 +8,15 @@ extern "C" int fz_pdfs_summarize(fz_ctx* c, double* pdfs, int64_t N, int64_t G, 
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, pgrid, urand, loss, widths, stats}));
-    const bool p_dev = is_device_ptr(pdfs), s_dev = is_device_ptr(stats), u_dev = is_device_ptr(urand), w_dev = is_device_ptr(widths);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, renormalize ? STAGE_INOUT : STAGE_IN);      // renormalised in place, pdf.py:985
+    const StageRows uv(c, urand, 8, c->d_lmap, STAGE_IN), wv(c, widths, 32, c->d_levid, STAGE_IN);
+    const bool s_dev = is_device_ptr(stats);
     // resident for the whole call: grid and loss matrix
     FZCHK(c->d_sgrid.ensure((size_t)G * 8)); FZCHK(copy_in(c, c->d_sgrid.p, pgrid, (size_t)G * 8));
     const double* d_loss = loss;
     if (!is_device_ptr(loss)) { FZCHK(c->d_sloss.ensure((size_t)G * G * 8)); FZCHK(copy_in(c, c->d_sloss.p, loss, (size_t)G * G * 8)); d_loss = c->d_sloss.as<double>(); }
     // chunk: staged pdf rows (if on the host) + risk rows + outputs
-    const int64_t per_obj = G * 8 * (p_dev ? 1 : 2) + 21 * 8 + 5 * 8;
+    const int64_t per_obj = G * 8 * (pv.dev ? 1 : 2) + 21 * 8 + 5 * 8;
     int64_t nc = std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / per_obj, (int64_t)1 << 20));
     nc = std::min(nc, N);
     const size_t lds_g = (size_t)2 * 2 * FZ_GEMM_BK * FZ_GEMM_LD * 8;
@@ -24,15 +26,8 @@ extern "C" int fz_pdfs_summarize(fz_ctx* c, double* pdfs, int64_t N, int64_t G, 
     HIPCHK(hipFuncSetAttribute((const void*)k_summarize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
-        double* dp;
-        if (p_dev) dp = pdfs + i0 * G;
-        else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        const double* du; const double* dw = nullptr;
-        if (u_dev) du = urand + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_lmap.p, urand + i0, (size_t)n * 8)); du = c->d_lmap.as<double>(); }
-        if (widths) {
-            if (w_dev) dw = widths + i0 * 4;
-            else { FZCHK(c->d_levid.ensure((size_t)n * 32)); FZCHK(copy_in(c, c->d_levid.p, widths + i0 * 4, (size_t)n * 32)); dw = c->d_levid.as<double>(); }
-        }
+        double* dp; const double* du; const double* dw;
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(uv.at(i0, n, &du)); FZCHK(wv.at(i0, n, &dw));
         FZCHK(c->d_pl[0].ensure((size_t)n * G * 8));                    // risk rows
         double* dr = c->d_pl[0].as<double>();
         double* ds; int64_t ostride;
@@ -47,7 +42,7 @@ extern "C" int fz_pdfs_summarize(fz_ctx* c, double* pdfs, int64_t N, int64_t G, 
                                c->d_sgrid.as<double>(), du, dw, wconf_scale, ostride, ds);
         }
         HIPCHK(hipGetLastError());
-        if (!p_dev && renormalize) FZCHK(copy_out(c, pdfs + i0 * G, dp, (size_t)n * G * 8));       // in place, pdf.py:985
+        FZCHK(pv.back(i0, n));
         if (!s_dev) for (int r = 0; r < 21; ++r) FZCHK(copy_out(c, stats + r * N + i0, ds + r * n, (size_t)n * 8));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -61,20 +56,17 @@ extern "C" int fz_overlap_nz(fz_ctx* c, const double* pdfs, int64_t N, int64_t G
     if ((pair_i >= 0) != (pair_j >= 0) || pair_i >= G || pair_j >= G) return fail(-3, "fz_overlap_nz: pair index out of range");
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, nz, overlap, lnlike}));
-    const bool p_dev = is_device_ptr(pdfs), o_dev = is_device_ptr(overlap);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), ov(c, overlap, 8, c->d_lmap, STAGE_OUT);
     FZCHK(c->d_sgrid.ensure((size_t)G * 8)); FZCHK(copy_in(c, c->d_sgrid.p, nz, (size_t)G * 8));
-    int64_t nc = p_dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 16), (int64_t)1 << 22));
+    int64_t nc = pv.dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 16), (int64_t)1 << 22));
     nc = std::min(nc, N);
     const int64_t nblk_max = (nc + 3) / 4;
     FZCHK(c->d_pl[1].ensure((size_t)nblk_max * 8 + 64));
     double total = 0.0;
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
-        const double* dp;
-        if (p_dev) dp = pdfs + i0 * G;
-        else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        double* dov;
-        if (o_dev) dov = overlap + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); dov = c->d_lmap.as<double>(); }
+        const double* dp; double* dov;
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(ov.at(i0, n, &dov));
         const int64_t nblk = (n + 3) / 4;
         double* part = c->d_pl[1].as<double>();
         {
@@ -87,11 +79,9 @@ extern "C" int fz_overlap_nz(fz_ctx* c, const double* pdfs, int64_t N, int64_t G
         double chunk = 0.0;
         FZCHK(copy_out(c, &chunk, part + nblk_max, 8));
         total += chunk;
-        if (!o_dev) FZCHK(copy_out(c, overlap + i0, dov, (size_t)n * 8));
+        FZCHK(ov.back(i0, n));
     }
-    if (is_device_ptr(lnlike)) HIPCHK(hipMemcpy(lnlike, &total, 8, hipMemcpyHostToDevice));
-    else *lnlike = total;
-    return 0;
+    return host_write(lnlike, &total, 8);
 }
 
 extern "C" int fz_pdfs_resample(fz_ctx* c, const double* pdfs, int64_t N, int64_t G, const double* old_grid, int64_t Gn,
@@ -101,7 +91,7 @@ extern "C" int fz_pdfs_resample(fz_ctx* c, const double* pdfs, int64_t N, int64_
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, old_grid, new_grid, out}));
-    const bool p_dev = is_device_ptr(pdfs), o_dev = is_device_ptr(out);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), ov(c, out, (size_t)Gn * 8, c->d_pl[0], STAGE_OUT);
     FZCHK(c->d_sgrid.ensure((size_t)(G + Gn) * 8));
     FZCHK(copy_in(c, c->d_sgrid.p, old_grid, (size_t)G * 8));
     FZCHK(copy_in(c, c->d_sgrid.as<double>() + G, new_grid, (size_t)Gn * 8));
@@ -110,15 +100,14 @@ extern "C" int fz_pdfs_resample(fz_ctx* c, const double* pdfs, int64_t N, int64_
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dp; double* dout;
-        if (p_dev) dp = pdfs + i0 * G; else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (o_dev) dout = out + i0 * Gn; else { FZCHK(c->d_pl[0].ensure((size_t)n * Gn * 8)); dout = c->d_pl[0].as<double>(); }
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(ov.at(i0, n, &dout));
         {
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
             hipLaunchKernelGGL(k_resample, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, dp, n, (int)G, c->d_sgrid.as<double>(),
                                (int)Gn, c->d_sgrid.as<double>() + G, left, right, renormalize, dout);
         }
         HIPCHK(hipGetLastError());
-        if (!o_dev) FZCHK(copy_out(c, out + i0 * Gn, dout, (size_t)n * Gn * 8));
+        FZCHK(ov.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -132,19 +121,17 @@ extern "C" int fz_nz_assign(fz_ctx* c, const double* pdfs, int64_t N, int64_t G,
     if (N <= 0 || G <= 0 || G >= ((int64_t)1 << 24)) return fail(-1, "fz_nz_assign: bad shape");
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {pdfs, nz, u, bins, counts}));
-    const bool p_dev = is_device_ptr(pdfs), u_dev = is_device_ptr(u), b_dev = is_device_ptr(bins), c_dev = is_device_ptr(counts);
+    const StageRows pv(c, pdfs, (size_t)G * 8, c->d_pdfs, STAGE_IN), uv(c, u, 8, c->d_lmap, STAGE_IN), bv(c, bins, 8, c->d_levid, STAGE_OUT, true);
+    const bool c_dev = is_device_ptr(counts);
     FZCHK(c->d_sgrid.ensure((size_t)G * 8)); FZCHK(copy_in(c, c->d_sgrid.p, nz, (size_t)G * 8));
     FZCHK(c->d_sloss.ensure((size_t)G * 8));
     HIPCHK(hipMemsetAsync(c->d_sloss.p, 0, (size_t)G * 8, c->stream));
-    int64_t nc = p_dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 32), (int64_t)1 << 22));
+    int64_t nc = pv.dev ? N : std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (G * 8 + 32), (int64_t)1 << 22));
     nc = std::min(nc, N);
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dp; const double* du; int64_t* db;
-        if (p_dev) dp = pdfs + i0 * G;
-        else { FZCHK(c->d_pdfs.ensure((size_t)n * G * 8)); FZCHK(copy_in(c, c->d_pdfs.p, pdfs + i0 * G, (size_t)n * G * 8)); dp = c->d_pdfs.as<double>(); }
-        if (u_dev) du = u + i0; else { FZCHK(c->d_lmap.ensure((size_t)n * 8)); FZCHK(copy_in(c, c->d_lmap.p, u + i0, (size_t)n * 8)); du = c->d_lmap.as<double>(); }
-        if (bins && b_dev) db = bins + i0; else { FZCHK(c->d_levid.ensure((size_t)n * 8)); db = c->d_levid.as<int64_t>(); }
+        FZCHK(pv.at(i0, n, &dp)); FZCHK(uv.at(i0, n, &du)); FZCHK(bv.at(i0, n, &db));
         {
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
             const size_t rows_lds = (size_t)4 * G * 8;          // four rows of p * nz (up to 48 KB: grids of 1 536 points; longer: no staging)
@@ -153,7 +140,7 @@ extern "C" int fz_nz_assign(fz_ctx* c, const double* pdfs, int64_t N, int64_t G,
                                c->d_sgrid.as<double>(), du, db, c->d_sloss.as<unsigned long long>(), staged);
         }
         HIPCHK(hipGetLastError());
-        if (bins && !b_dev) FZCHK(copy_out(c, bins + i0, db, (size_t)n * 8));
+        FZCHK(bv.back(i0, n));
     }
     if (c_dev) HIPCHK(hipMemcpyAsync(counts, c->d_sloss.p, (size_t)G * 8, hipMemcpyDeviceToDevice, c->stream));
     else FZCHK(copy_out(c, counts, c->d_sloss.p, (size_t)G * 8));

@@ -70,7 +70,7 @@ extern "C" int fz_synphot(fz_ctx* c, int64_t Npair, const int64_t* tmpl, const d
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {out}));
     const int Nf = (int)c->sp_Nf;
-    const bool o_dev = is_device_ptr(out);
+    const StageRows ov(c, out, (size_t)Nf * 8, c->d_pl[0], STAGE_OUT);
     const fz::SynView v = syn_view(c);
     // chunks of pairs in the caller's order, each sorted by template on its own: a pair's result is one wave's work whatever the cut
     int64_t nc = std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / ((int64_t)Nf * 8 + (int64_t)sizeof(fz::SynPair) + 16), (int64_t)1 << 24));
@@ -100,8 +100,8 @@ extern "C" int fz_synphot(fz_ctx* c, int64_t Npair, const int64_t* tmpl, const d
             a = b;
         }
         FZCHK(c->d_net[0].ensure((size_t)n * sizeof(fz::SynPair))); FZCHK(copy_in(c, c->d_net[0].p, pairs.data(), (size_t)n * sizeof(fz::SynPair)));
-        double* dout = out + i0 * Nf;
-        if (!o_dev) { FZCHK(c->d_pl[0].ensure((size_t)n * Nf * 8)); dout = c->d_pl[0].as<double>(); }
+        double* dout;
+        FZCHK(ov.at(i0, n, &dout));
         for (int which = 0; which < 2; ++which) {
             const int ni = (int)items[which].size();
             if (!ni) continue;
@@ -119,7 +119,7 @@ extern "C" int fz_synphot(fz_ctx* c, int64_t Npair, const int64_t* tmpl, const d
             }
         }
         HIPCHK(hipGetLastError());
-        if (!o_dev) FZCHK(copy_out(c, out + i0 * Nf, dout, (size_t)n * Nf * 8));
+        FZCHK(ov.back(i0, n));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;

@@ -1,10 +1,9 @@
-// ---- what fz_som_train and fz_gng_train share on the host (fz_train.h; NetStage: fz_net_host.inc) ----------------------------
+// ---- what fz_som_train and fz_gng_train share on the host (fz_train.h; StageWhole: fz_stage.h) ----------------------------
 namespace {
 // the rows drawn at the steps [s0, s1) must exist: this keeps every model-row access of the kernel in bounds
 int check_draws(const char* name, const int64_t* draws, int64_t s0, int64_t s1, int64_t M) {
     std::vector<int64_t> dr((size_t)(s1 - s0));
-    if (is_device_ptr(draws)) HIPCHK(hipMemcpy(dr.data(), draws + s0, dr.size() * 8, hipMemcpyDeviceToHost));
-    else std::memcpy(dr.data(), draws + s0, dr.size() * 8);
+    FZCHK(host_read(dr.data(), draws + s0, dr.size() * 8));
     for (int64_t j : dr)
         if (j < 0 || j >= M) return fail(-3, "%s: drawn row %lld outside [0, %lld)", name, (long long)j, (long long)M);
     return 0;
@@ -30,7 +29,7 @@ int train_rowk(fz_ctx* c, Args& a, int64_t M) {
 // The row kernel, the ONE persistent workgroup of the trainer (a thread per node up to TRAIN_NT, in whole waves) and the staged
 // outputs back to the host.  `a` is complete except for rowk.
 template <class Args>
-int train_run(fz_ctx* c, NetStage& st, void (*kernel)(Args), Args& a, int64_t M, int nodes, size_t lds) {
+int train_run(fz_ctx* c, StageWhole& st, void (*kernel)(Args), Args& a, int64_t M, int nodes, size_t lds) {
     FZCHK(train_rowk(c, a, M));
     const int nt = nodes >= TRAIN_NT ? TRAIN_NT : ((nodes + 63) / 64) * 64;
     HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
