@@ -68,6 +68,8 @@ ABI = {
     "fz_timing_get": (C.c_int, [_P, C.POINTER(Timing)]),
     "fz_last_form": (C.c_char_p, [_P]),
     "fz_set_workspace_limit": (C.c_int, [_P, _I64]),
+    "fz_get_workspace_limit": (_I64, [_P]),
+    "fz_cu_count": (C.c_int, [_P]),
     "fz_set_producer_stream": (C.c_int, [_P, _P, _I32]),
     "fz_host_alloc": (C.c_int, [_I64, C.POINTER(_P)]),
     "fz_host_free": (C.c_int, [_P]),

@@ -154,6 +154,8 @@ extern "C" int fz_modec_niter(fz_ctx* c, int64_t n, int32_t* out) {
     HIPCHK(hipSetDevice(c->device));
     return copy_out(c, out, c->d_mcniter.p, (size_t)n * 4);
 }
+extern "C" int64_t fz_get_workspace_limit(fz_ctx* c) { return c ? c->ws_limit : -1; }
+extern "C" int fz_cu_count(fz_ctx* c) { return c ? c->cu_count : -1; }
 extern "C" int fz_set_workspace_limit(fz_ctx* c, int64_t bytes) {
     if (!c || bytes < (1 << 20)) return fail(-1, "fz_set_workspace_limit: need >= 1 MiB");
     c->ws_limit = bytes; return 0;

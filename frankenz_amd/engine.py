@@ -534,6 +534,14 @@ class Engine(object):
     def set_workspace_limit(self, nbytes):
         check(self.lib.fz_set_workspace_limit(self.h, int(nbytes)))
 
+    def workspace_limit(self):
+        """the workspace budget in force, in bytes"""
+        return int(self.lib.fz_get_workspace_limit(self.h))
+
+    def cu_count(self):
+        """compute units of the engine's device"""
+        return int(self.lib.fz_cu_count(self.h))
+
 
 class DeviceArray(object):
     """A C-contiguous array in an engine's device memory (fz_dev_alloc), with the few tensor-like members the host layer looks at

@@ -107,6 +107,10 @@ const char* fz_last_form(fz_ctx* ctx);
 /* byte budget for internal work space (candidate lists of the single-pass kernel, (N x M)
  * planes of mode C, host staging); default 45 % of the device memory, allocated on demand. */
 int  fz_set_workspace_limit(fz_ctx* ctx, int64_t bytes);
+/* the budget in force, in bytes, and the compute units of the context's device: the fused kernels choose their launch geometry and
+ * between one pass and two from these (callers that change the budget put the value they found back); -1: NULL ctx */
+int64_t fz_get_workspace_limit(fz_ctx* ctx);
+int  fz_cu_count(fz_ctx* ctx);
 /* Where device-resident INPUTS of the following calls come from (no reference counterpart: the reference has no device).
  * mode 0 (default): unknown -- every entry point handed device pointers drains the whole device first (hipDeviceSynchronize).
  * mode 1: they are produced by work queued on `stream` (a hipStream_t; NULL = the legacy default stream): the library records an
