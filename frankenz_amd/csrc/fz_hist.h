@@ -273,7 +273,7 @@ template <class SRC, int TW, int NW, bool EXACT, bool OBJK = (SRC::NB > 8), bool
 __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __restrict__ kvp, int acc_stride, int64_t N, int M,
                                                    double wt_thresh, int normalize, Cand* __restrict__ amb, int64_t cap,
                                                    double* __restrict__ lmap, double* __restrict__ levid, double* __restrict__ pdfs,
-                                                   const int* __restrict__ omap, int* __restrict__ redo) {
+                                                   const int* __restrict__ omap, int* __restrict__ redo, const int* __restrict__ order) {
     constexpr int TILE = hist_tile<SRC>(), RW = SRC::RW, TDR = RW * TILE, TD = TDR + TILE / 2, NT = NW * 64, OD = SRC::OBJ_DOUBLES;
     constexpr int WP = SRC::WPOW, BT = SRC::NB;
     static_assert(!OBJK || TW == 1, "per-object band counts: one object per wave");
@@ -364,6 +364,14 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         else return hist_exactw<WP, decltype(small)::value>(c2, t);
     };
     double lref = uniform_d(lnl_c2(K));                           // ln L at the mode: the reference of every weight
+    // object slot -> object: through `order` first (the launch's slots in the order of their expected cost, fz_hist_order.h: the screen
+    // form without segments; every other form is compiled without the read), then through the launch's object map as before
+    auto obj_of = [&](int64_t s) -> int64_t {
+        if constexpr (!EXACT && !SEG) {
+            if (order) { const int64_t q = (int64_t)order[s]; s = q < 0 ? 0 : (q < N ? q : N - 1); }      // (a permutation of [0, N): the clamp never acts)
+        }
+        return omap ? (int64_t)omap[s] : s;
+    };
 
     for (int64_t rnd = 0; rnd < nrounds; ++rnd) {
         const int64_t g = gw + rnd * nwaves;
@@ -372,7 +380,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
 #pragma unroll
         for (int o = 0; o < TW; ++o) {
             const int64_t os = i0 + o < N ? i0 + o : N - 1;
-            src.park_obj(omap ? (int64_t)omap[os] : os, objs + o * OD, lane);
+            src.park_obj(obj_of(os), objs + o * OD, lane);
         }
         for (int k = lane; k < TW * acc_stride; k += 64) rows[k] = 0.0;
         // SEG: state of the pattern in force (set by seg_switch below)
@@ -389,7 +397,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         };
         if constexpr (SEG) {
             const int64_t os = i0 < N ? i0 : N - 1;
-            const int64_t oi = omap ? (int64_t)omap[os] : os;
+            const int64_t oi = obj_of(os);
             src.park_obj(oi, obj0, lane);
             if constexpr ((SRC::LMODE == 1 || SRC::LMODE == 2) && FZ_HIST_CHI2_2OP && !(SRC::LMODE == 2 && SRC::SAFE)) {
                 // the two-instruction chi2's units (s = sqrt(1 / var), xs = x s; below) once per object, not at every change of pattern
@@ -421,8 +429,8 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         }
         if constexpr (OBJK && !SEG) {
             const int64_t os = i0 < N ? i0 : N - 1;
-            const int nb = __builtin_amdgcn_readfirstlane(__popc(src.ov.bits[omap ? (int64_t)omap[os] : os]));   // observed bands (pad bits are 0)
-            const int64_t oi = omap ? (int64_t)omap[os] : os;
+            const int64_t oi = obj_of(os);
+            const int nb = __builtin_amdgcn_readfirstlane(__popc(src.ov.bits[oi]));   // observed bands (pad bits are 0)
             wpr = nb - (SRC::LMODE == 2 ? 3 : 2);
             // power 0 (two observed bands; three with the free scale): L = e^{-chi2/2} / C, largest at chi2 = 0 -- still bounded by its
             // value at the mode, so the same scheme holds with K = 0.  Below that the likelihood is unbounded at chi2 -> 0: the sweep.
@@ -902,7 +910,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                                 if ((sw & 0x3fff) != segcur) {                     // a few dozen times per pass; nothing waits in the buffer
                                     if (mcw && segcur >= 0) {
                                         const int rko = kv.seg_rank[segcur];
-                                        if (kv.seg_rank[sw & 0x3fff] != rko) class_flush(rko, rows, pdfs + (omap ? (int64_t)omap[i0] : i0) * kv.G);
+                                        if (kv.seg_rank[sw & 0x3fff] != rko) class_flush(rko, rows, pdfs + obj_of(i0) * kv.G);
                                     }
                                     seg_switch(sw);
                                 }
@@ -961,7 +969,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
 #pragma unroll 1
             for (int o = 0; o < TW; ++o) {
                 if (i0 + o >= N) break;
-                const int64_t i = omap ? (int64_t)omap[i0 + o] : i0 + o;
+                const int64_t i = obj_of(i0 + o);
                 double* row = rows + o * acc_stride;
                 double wbest_run = 0.0;
                 if constexpr (!EXACT) {

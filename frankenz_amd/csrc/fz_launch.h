@@ -4,6 +4,7 @@
 #include "fz_kernels.h"
 #include "fz_nolist.h"
 #include "fz_hist.h"
+#include "fz_hist_order.h"
 #include "fz_plane.h"
 
 // ---- launch helpers ------------------------------------------------------------
@@ -436,9 +437,19 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
     FZCHK(c->d_redo.ensure(((size_t)n + 1) * sizeof(int)));
     HIPCHK(hipMemsetAsync(c->d_redo.p, 0, sizeof(int), c->stream));
     FZCHK(fz_upload_kv(c, kv, &kvs));
+    // the screen form without segments, more than one round: the slots are dealt in the order of their expected settle cost
+    // (fz_hist_order.h), computed here from this launch's objects -- nothing is kept from call to call.  FZ_HIST_ORDER=0 deals them in
+    // catalogue order as every other form does; FZ_HIST_ORDER_STRIDE / _OFFSET: the model sample (every 256th from the first).
+    bool dealt = false;
+    if constexpr (!EXACT && !SEG) dealt = n > blocks * NW * TW && n < ((int64_t)1 << 31) && fz_dbg_int("FZ_HIST_ORDER", 1) != 0;
+    const int* order = nullptr;
     Timer t(c, &c->tm.ms_fused, &c->tm.n_fused);
+    if constexpr (!EXACT && !SEG) {
+        if (dealt) FZCHK((fz_hist_order_build<SRC, OBJK>(c, src, n, M, ko->wt_thresh, fz_dbg_int("FZ_HIST_ORDER_STRIDE", 256),
+                                                         fz_dbg_int("FZ_HIST_ORDER_OFFSET", 0), &order)));
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, src, c->d_kv.as<fz::KdeView>(), kv.acc_stride, n,
-                       (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<fz::Cand>(), acap, lmap, levid, pdfs, c->omap, c->d_redo.as<int>());
+                       (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<fz::Cand>(), acap, lmap, levid, pdfs, c->omap, c->d_redo.as<int>(), order);
     if (sweep_ok) {
         SWS sws;
         if constexpr (std::is_same<SWS, SRC>::value) sws = src; else sws = *swsp;
