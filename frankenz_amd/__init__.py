@@ -8,7 +8,7 @@ C ABI in ``include/frankenz_hip.h`` (``libfrankenz_hip.so``, loaded with ctypes)
 There is no CPU fallback: importing the engine without the built library raises.
 """
 from .pdf import (PDFDict, gaussian, gauss_kde, gauss_kde_dict, loglike, logprob, logprob_prior,
-                  logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize)
+                  logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize, sample_labels)
 from .bruteforce import BruteForce
 from .knn import NearestNeighbors
 from . import fitting, networks, pdf, plotting, priors, reddening, samplers, simulate
@@ -16,4 +16,4 @@ from . import fitting, networks, pdf, plotting, priors, reddening, samplers, sim
 __version__ = "0.1.0"
 __all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gauss_kde",
            "gauss_kde_dict", "loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "luptitude", "magnitude",
-           "pdfs_resample", "pdfs_summarize", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]
+           "pdfs_resample", "pdfs_summarize", "sample_labels", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]

@@ -129,6 +129,11 @@ ABI = {
     "fz_synphot_upload": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "fz_synphot": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _P]),
     "fz_prior_rows_from_grid": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "fz_draw_logwt": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, C.c_uint32, C.c_uint32, _I64, _I64, _P, _P, _P]),
+    "fz_fit_draw": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _P, C.c_uint32, C.c_uint32, _I64, _I64,
+                              _P, _P, _P]),
+    "fz_knn_search_fit_draw": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F64, _F64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _P,
+                                         C.c_uint32, C.c_uint32, _I64, _I64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -76,6 +76,62 @@ def _progress(verbose, what, i, n):
         sys.stderr.flush()
 
 
+def _draw_uniforms(rstate, draws, Ndata, Nsamples):
+    """-> ``(u, key)`` of a ``fit_sample`` / ``sample`` call, named as in ``samplers.hierarchical_sampler``: ``draws='host'``
+    takes ``u = rstate.rand(Ndata, Nsamples)``; ``draws='device'`` a two-word Philox key ``rstate.randint(0, 2**32, 2)``, the
+    device drawing at the counter (object, draw) -- ``samplers._philox_uniform(key, draw, Ndata)`` reproduces the uniforms."""
+    if draws not in ('host', 'device'):
+        raise ValueError("`draws` must be 'host' or 'device' (got %r)" % (draws,))
+    if rstate is None:
+        rstate = np.random
+    if draws == 'host':
+        return np.ascontiguousarray(rstate.rand(Ndata, Nsamples)), None
+    return None, rstate.randint(0, 2**32, size=2, dtype=np.uint32)
+
+
+def _check_nsamples(Nsamples):
+    if int(Nsamples) != Nsamples or Nsamples < 1:
+        raise ValueError("`Nsamples` must be a whole number >= 1 (got %r)" % (Nsamples,))
+    return int(Nsamples)
+
+
+def _is_kind(a, kind):
+    """``a`` holds 8-byte items of dtype ``kind`` (a device array that carries no dtype is taken at its item size)"""
+    dt = getattr(a, "dtype", None)
+    return a.element_size() == 8 if dt is None else str(dt).split('.')[-1] == kind
+
+
+def _draw_outputs(eng, out, Ndata, Nsamples, like=None):
+    """``(idx, lmap, levid)`` of a draw call: the caller's ``out=(idx[, lmap, levid])`` checked, else fresh arrays of the kind
+    ``like`` is (a device array: device arrays of the same kind; None / NumPy: NumPy)"""
+    shapes = ((Ndata, Nsamples), (Ndata,), (Ndata,))
+    kinds = ('int64', 'float64', 'float64')
+    if out is not None:
+        out = tuple(out)
+        if len(out) not in (1, 3):
+            raise ValueError("`out` must be (idx,) or (idx, lmap, levid)")
+        for a, shp, kind in zip(out, shapes, kinds):
+            if tuple(a.shape) != shp or not _is_kind(a, kind):
+                raise ValueError("`out` must hold an int64 (Ndata, Nsamples) array and float64 (Ndata,) arrays; got %s %s"
+                                 % (tuple(a.shape), getattr(a, "dtype", None)))
+            if (hasattr(a, "is_contiguous") and not a.is_contiguous()) or (isinstance(a, np.ndarray) and not a.flags.c_contiguous):
+                raise ValueError("`out` arrays must be C-contiguous")
+        return out + (None,) * (3 - len(out))
+    if like is not None and hasattr(like, "data_ptr"):
+        if hasattr(like, "is_cuda"):
+            import torch
+            return tuple(torch.empty(shp, dtype=getattr(torch, kind), device=like.device) for shp, kind in zip(shapes, kinds))
+        return tuple(eng.device_empty(shp, np.dtype(kind)) for shp, kind in zip(shapes, kinds))
+    return np.empty(shapes[0], dtype=np.int64), np.zeros(Ndata), np.zeros(Ndata)
+
+
+def _device_objects(data, data_err, data_mask):
+    for a in (data, data_err, data_mask):
+        if not hasattr(a, "data_ptr") or tuple(a.shape) != tuple(data.shape) or len(data.shape) != 2 or not a.is_contiguous() \
+                or not _is_kind(a, 'float64'):
+            raise ValueError("device objects must be contiguous float64 arrays of one (Ndata, Nfilt) shape")
+
+
 class _Prepared(object):
     """A model set + labels resident on the device and the option structs of one ``fit_predict`` configuration
     (``BruteForce.prepare_fit_predict``)."""
@@ -164,6 +220,7 @@ class BruteForce():
         self.fit_scale_err = None
         self._device = device
         self._ndata_all = None
+        self.philox_key = None      # key of the last fit_sample / sample call with draws='device'
 
     # ------------------------------------------------------------------
     def _engine(self):
@@ -359,6 +416,82 @@ class BruteForce():
             eng.predict_logwt(lw, ko, pdfs, lmap, levid)
             for i in range(hi - lo):
                 yield pdfs[i], (lmap[i], levid[i])
+
+    # ------------------------------------------------------------------
+    def fit_sample(self, data, data_err, data_mask, Nsamples, lprob_func=None, lprob_args=None, lprob_kwargs=None, rstate=None,
+                   draws='device', return_gof=False, verbose=True, out=None):
+        """Extension (no reference counterpart; docs/draws.md): ``Nsamples`` posterior draws over the model set per object,
+        ``j ~ P(j | i) = exp(lnprob_ij - levid_i)`` -- the object's posterior as what it is, a weighted set of models, in
+        8 * Nsamples bytes.  Returns the ``(Ndata, Nsamples)`` int64 model indices (``-1`` throughout a row whose ln-posterior
+        holds a nan or has no finite maximum), with ``return_gof`` also ``(lmap, levid)``.  ``pdf.sample_labels(idx, labels)``
+        turns them into draws of ANY label afterwards.
+
+        ``lprob_func`` as in ``fit_predict`` (``logprob_prior`` / ``logprob_prior_lerp`` / ``priors.logprob_bpz`` run on the
+        device; any other callable runs per object on the host and its ln-posterior rows are drawn from on the device).
+        ``draws`` / ``rstate``: see ``_draw_uniforms``; the Philox key of the call is kept in ``philox_key``.  ``out=(idx[, lmap,
+        levid])`` and device arrays for ``data`` work as in ``fit_predict(out=)`` (built-in likelihood only); objects are cleaned
+        in place.  A draw depends on its object's ln-posterior row and uniform alone: chunking and object order do not change it."""
+        prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
+        S = _check_nsamples(Nsamples)
+        on_dev = hasattr(data, "data_ptr")
+        if host is not None and (out is not None or on_dev):
+            raise NotImplementedError("device arrays / `out=` need the built-in likelihood")
+        Ndata = int(data.shape[0]) if on_dev else len(data)
+        u, key = _draw_uniforms(rstate, draws, Ndata, S)
+        self.philox_key = key
+        if host is not None:
+            eng = get_engine(self._device)
+            idx, lmap, levid = _draw_outputs(eng, None, Ndata, S)
+            for lo in range(0, Ndata, _HOST_CHUNK):
+                hi = min(Ndata, lo + _HOST_CHUNK)
+                plane = np.empty((hi - lo, self.NMODEL))
+                for i in range(lo, hi):
+                    plane[i - lo] = host(data[i], data_err[i], data_mask[i], self)[2]
+                    _progress(verbose, 'Sampling object', i + 1, Ndata)
+                eng.draw_logwt(plane, S, idx[lo:hi], u=None if u is None else u[lo:hi], key=key, first=lo, lmap=lmap[lo:hi],
+                               levid=levid[lo:hi], n=hi - lo)
+        else:
+            opts = like_opts(lprob_kwargs)
+            eng = self._engine()
+            self._ndata_all = Ndata
+            if on_dev:
+                _device_objects(data, data_err, data_mask)
+                x, xe, xm, obj = data, data_err, data_mask, None
+            else:
+                obj = HostObjects(data, data_err, data_mask)
+                x, xe, xm = obj.x, obj.xe, obj.xm
+            idx, lmap, levid = _draw_outputs(eng, out, Ndata, S, like=data if on_dev else None)
+            if Ndata:
+                eng.fit_draw(x, xe, xm, opts, prior.chunk(0, Ndata, Ndata) if prior is not None else None, S, idx, u=u, key=key,
+                             lmap=lmap, levid=levid, n=Ndata)
+            if obj is not None:
+                obj.writeback()
+            _progress(verbose, 'Sampling object', Ndata, Ndata)
+        if verbose:
+            sys.stderr.write('\n')
+            sys.stderr.flush()
+        return (idx, (lmap, levid)) if return_gof else idx
+
+    def sample(self, Nsamples, logwt=None, rstate=None, draws='device', return_gof=False):
+        """Extension, the analogue of ``predict``: ``Nsamples`` draws per object from stored fits (``fit_lnprob``) or the given
+        ``(Ndata, Nmodel)`` rows of ln-weights (NumPy or a device array).  ``fit()`` followed by ``sample()`` gives what
+        ``fit_sample`` gives."""
+        S = _check_nsamples(Nsamples)
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        lw = logwt if hasattr(logwt, "data_ptr") else np.ascontiguousarray(logwt, dtype=np.float64)
+        if len(lw.shape) != 2 or (hasattr(lw, "data_ptr") and not (_is_kind(lw, 'float64') and lw.is_contiguous())):
+            raise ValueError("`logwt` must be a C-contiguous float64 (Ndata, Nmodel) array; got shape %s" % (tuple(lw.shape),))
+        Ndata = int(lw.shape[0])
+        u, key = _draw_uniforms(rstate, draws, Ndata, S)
+        self.philox_key = key
+        eng = get_engine(self._device)
+        idx, lmap, levid = _draw_outputs(eng, None, Ndata, S, like=lw)
+        if Ndata:
+            eng.draw_logwt(lw, S, idx, u=u, key=key, lmap=lmap, levid=levid, n=Ndata, W=int(lw.shape[1]))
+        return (idx, (lmap, levid)) if return_gof else idx
 
     # ------------------------------------------------------------------
     def fit_predict(self, data, data_err, data_mask, model_labels, model_label_errs,

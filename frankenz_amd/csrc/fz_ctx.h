@@ -136,6 +136,9 @@ struct fz_ctx {
     // synthetic photometry (fz_synphot_upload): the ragged filter and template tables in one block, and the host copy of their offsets
     int64_t sp_Nf = 0, sp_Nt = 0; std::vector<int64_t> h_sp_foff, h_sp_toff;
     DevBuf d_sp;
+    // posterior draws (fz_draw_host.inc): neighbours, counts, ln-like and ln-prob rows of a k-NN chunk (or a host caller's staged rows,
+    // neighbours and counts), the caller's uniforms, the drawn indices
+    DevBuf d_draw[6];
 
     std::vector<DevBuf*> all_bufs() {
         std::vector<DevBuf*> v = {&d_y, &d_ye2, &d_ye, &d_rec0, &d_rec1, &d_ye2c, &d_mbits, &d_lgA, &d_lgB, &d_widths, &d_offsets, &d_kern, &d_pos,
@@ -145,6 +148,7 @@ struct fz_ctx {
         for (auto& b : d_pl) v.push_back(&b);
         for (auto& b : d_net) v.push_back(&b);
         for (auto& b : d_mc) v.push_back(&b);
+        for (auto& b : d_draw) v.push_back(&b);
         return v;
     }
 };

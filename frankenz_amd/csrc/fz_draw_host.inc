@@ -1,0 +1,174 @@
+// Host side of the posterior draws (fz_draw.h; docs/draws.md): fz_draw_logwt, fz_fit_draw, fz_knn_search_fit_draw.
+// Included by frankenz_hip.hip after the entry points it builds on (prep_chunk, prior_*, run_planes, run_modec, the k-NN calls).
+
+static int draw_limits(const char* who, int64_t L, int64_t S) {
+    if (S < 1) return fail(-4, "%s: Nsamples = %lld, need at least 1", who, (long long)S);
+    if (S > FZ_DRAW_SMAX) return fail(-5, "%s: Nsamples = %lld exceeds FZ_DRAW_SMAX = %d", who, (long long)S, FZ_DRAW_SMAX);
+    if (L < 1) return fail(-4, "%s: rows of %lld entries", who, (long long)L);
+    if (L > FZ_DRAW_LMAX) return fail(-5, "%s: rows of %lld entries exceed FZ_DRAW_LMAX = %d", who, (long long)L, FZ_DRAW_LMAX);
+    return 0;
+}
+
+// n rows of L ln-weights in device memory -> idx (n, S), lmap, levid (device; the last two may be nullptr).  u (n, S) on the device, or
+// nullptr: Philox under (k0, k1), object `first` + row.  The geometry is a function of L alone (FZ_DRAW_WPO = 1 / 4 forces one: tests).
+static int run_draw(fz_ctx* c, int64_t n, int64_t L, const double* rows, const int64_t* nbr, const int64_t* nnb, const double* u, uint32_t k0,
+                    uint32_t k1, int64_t first, int64_t S, int64_t* idx, double* lmap, double* levid) {
+    if (u) {
+        int bad = 0;
+        const int64_t tot = n * S;
+        FZCHK(fz_flag_roundtrip(c, bad, [&](int* d_flags) {
+            hipLaunchKernelGGL(fz::k_draw_check_u, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, u, tot, d_flags);
+            return 0;
+        }));
+        if (bad) return fail(-4, "posterior draws: a uniform outside [0, 1]");
+    }
+    int wpo = L <= FZ_DRAW_WAVE_LMAX ? 1 : 4;
+    const long long forced = fz_dbg_int("FZ_DRAW_WPO", 0);
+    if (forced == 1 || forced == 4) wpo = (int)forced;
+    const int opb = 4 / wpo;
+    const size_t nsegL = (size_t)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
+    const size_t lds = (FZ_DRAW_HDR + (size_t)opb * 2 * nsegL) * 8;
+    if (lds > FZ_LDS_BYTES) return fail(-5, "posterior draws: rows of %lld entries need %zu bytes of LDS at this geometry", (long long)L, lds);
+    const void* kern = wpo == 1 ? (const void*)fz::k_draw<1> : (const void*)fz::k_draw<4>;
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int ef = 0;
+    FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
+        Timer t(c, &c->tm.ms_other, &c->tm.n_other);
+        const dim3 grid((unsigned)((n + opb - 1) / opb)), blk(256);
+        if (wpo == 1) hipLaunchKernelGGL(fz::k_draw<1>, grid, blk, lds, c->stream, rows, n, L, nbr, nnb, u, k0, k1, first, (int)S, idx, lmap, levid, d_flags);
+        else hipLaunchKernelGGL(fz::k_draw<4>, grid, blk, lds, c->stream, rows, n, L, nbr, nnb, u, k0, k1, first, (int)S, idx, lmap, levid, d_flags);
+        return 0;
+    }));
+    if (ef) return fail(-3, "posterior draws: Nneighbors outside [0, %lld]", (long long)L);
+    return 0;
+}
+
+// the draw's own arguments, staged chunk by chunk: u in, idx / lmap / levid out
+struct DrawArgs {
+    StageRows uv, iv, lmv, lev;
+    DrawArgs(fz_ctx* c, const double* u, int64_t S, int64_t* idx, double* lmap, double* levid)
+        : uv(c, u, (size_t)S * 8, c->d_draw[4], STAGE_IN), iv(c, idx, (size_t)S * 8, c->d_draw[5], STAGE_OUT),
+          lmv(c, lmap, 8, c->d_lmap, STAGE_OUT), lev(c, levid, 8, c->d_levid, STAGE_OUT) {}
+    int64_t staged_bytes_per_obj() const { return (int64_t)((uv.staged() ? uv.row : 0) + (iv.staged() ? iv.row : 0) + 16); }
+    int run(fz_ctx* c, int64_t i0, int64_t n, int64_t L, const double* rows, const int64_t* nbr, const int64_t* nnb, uint32_t k0, uint32_t k1,
+            int64_t first, int64_t S) const {
+        const double* du; int64_t* di; double *dm, *de;
+        FZCHK(uv.at(i0, n, &du)); FZCHK(iv.at(i0, n, &di)); FZCHK(lmv.at(i0, n, &dm)); FZCHK(lev.at(i0, n, &de));
+        FZCHK(run_draw(c, n, L, rows, nbr, nnb, du, k0, k1, first + i0, S, di, dm, de));
+        FZCHK(iv.back(i0, n)); FZCHK(lmv.back(i0, n)); FZCHK(lev.back(i0, n));
+        return 0;
+    }
+};
+
+extern "C" int fz_draw_logwt(fz_ctx* c, const double* logwt, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr,
+                             const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
+                             double* levid) {
+    if (!c || !logwt || !idx) return fail(-1, "fz_draw_logwt: NULL argument");
+    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "fz_draw_logwt: neighbors and nnbr come together");
+    FZCHK(draw_limits("fz_draw_logwt", W, S));
+    if (N <= 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    FZCHK(wait_for_producers(c, {logwt, neighbors, nnbr, u, idx, lmap, levid}));
+    const StageRows rv(c, logwt, (size_t)W * 8, c->d_draw[2], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_draw[0], STAGE_IN),
+        cv(c, nnbr, 8, c->d_draw[1], STAGE_IN);
+    const DrawArgs da(c, u, S, idx, lmap, levid);
+    const int64_t per_obj = (rv.staged() ? W * 8 : 0) + (nv.staged() ? W * 8 + 8 : 0) + da.staged_bytes_per_obj();
+    int64_t nc = std::max<int64_t>(1, c->ws_limit / per_obj);
+    nc = std::min<int64_t>(std::min<int64_t>(nc, N), 1 << 18);
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t n = std::min(nc, N - i0);
+        const double* dr; const int64_t* dn; const int64_t* dc;
+        FZCHK(rv.at(i0, n, &dr)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc));
+        FZCHK(da.run(c, i0, n, W, dr, dn, dc, key0, key1, first, S));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// objects -> draws with the built-in likelihood: the materialised route of fit_predict_impl's CDF rule (planes, or mode C's final
+// ln-like plane; + the ln-prior), chunked from the workspace limit in the same way, with the draw kernel as the rows' consumer
+extern "C" int fz_fit_draw(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, const fz_prior_lerp* pr,
+                           const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
+                           double* levid) {
+    if (!c || !x || !xe || !xm || !o || !idx) return fail(-1, "fz_fit_draw: NULL argument");
+    if (!c->M) return fail(-1, "fz_fit_draw: models have not been uploaded");
+    FZCHK(draw_limits("fz_fit_draw", c->M, S));
+    if (N <= 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    FZCHK(wait_for_producers(c, {x, xe, xm, pr ? pr->table : nullptr, pr ? pr->rows : nullptr, pr ? pr->frac : nullptr, u, idx, lmap, levid}));
+    const int mode = eff_mode(c, like_mode(o));
+    const int64_t M = c->M;
+    PriorBind pb; PriorGuard guard{c};
+    FZCHK(prior_begin(c, pr, N, M, pb));
+    const DrawArgs da(c, u, S, idx, lmap, levid);
+    int64_t nc = std::min<int64_t>(N, fz_dbg_int("FZ_CHUNK", 1 << 20));
+    const int64_t per_obj = M * 8 * (mode == 3 ? 4 : 1) + pb.chunk_bytes_per_obj + da.staged_bytes_per_obj();
+    nc = std::min<int64_t>(nc, std::max<int64_t>(1, c->ws_limit / per_obj));
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t n = std::min(nc, N - i0);
+        ObjChunk ch; int fl = 0;
+        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
+        FZCHK(prior_chunk(c, pb, i0, n, M));
+        const int var = pick_var(c, fl);
+        double* lpl;
+        if (mode == 3) {
+            c->mc_lnl_only = 1;
+            FZCHK(run_modec(c, var, n, o));
+            lpl = c->d_mc[1].as<double>();
+            if (!c->mc_lnl_only) FZCHK(modec_final(c, n, var != VAR_FAST, o, lpl, nullptr, nullptr, nullptr, nullptr));
+            c->mc_lnl_only = 0;
+        } else {
+            FZCHK(c->d_pl[0].ensure((size_t)n * M * 8));
+            lpl = c->d_pl[0].as<double>();
+            FZCHK(run_planes(c, mode, var, o->dim_prior, n, lpl, nullptr, nullptr, nullptr, nullptr));
+        }
+        if (c->prior.tab) FZCHK(prior_add(c, lpl, n, M, nullptr, nullptr, nullptr, lpl));
+        FZCHK(da.run(c, i0, n, M, lpl, nullptr, nullptr, key0, key1, first, S));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// query features + objects -> draws over each object's neighbour subset, without the KDE half: per chunk the searches and the subset
+// likelihood of fz_knn_search_fit_predict_prior_lerp (its padded ln-prob rows, neighbours and counts stay on the device), then the
+// draw kernel on those rows.  neighbors (N, K k) / nnbr (N): optional outputs, as there.
+extern "C" int fz_knn_search_fit_draw(fz_ctx* c, const double* q, double* x, double* xe, double* xm, int64_t N, int32_t k, double lp_norm,
+                                      double dub, const fz_like_opts* o, const fz_prior_lerp* pr, const double* u, uint32_t key0,
+                                      uint32_t key1, int64_t first, int64_t S, int64_t* neighbors, int64_t* nnbr, int64_t* idx,
+                                      double* lmap, double* levid) {
+    if (!c || !q || !x || !xe || !xm || !o || !idx) return fail(-1, "fz_knn_search_fit_draw: NULL argument");
+    if (!c->knn_K) return fail(-1, "fz_knn_search_fit_draw: feature sets have not been uploaded");
+    if (k <= 0) return fail(-5, "fz_knn_search_fit_draw: k=%d unsupported", k);
+    const int64_t W = (int64_t)c->knn_K * k, M = c->M;
+    const int F = c->knn_F, B = c->B;
+    FZCHK(draw_limits("fz_knn_search_fit_draw", W, S));
+    if (N <= 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const bool has_prior = pr && pr->table;
+    const DrawArgs da(c, u, S, idx, lmap, levid);
+    const int64_t nc = std::min<int64_t>(N, std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (W * 48 + da.staged_bytes_per_obj()), 1 << 17)));
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t n = std::min(nc, N - i0);
+        FZCHK(c->d_draw[0].ensure((size_t)n * W * 8)); FZCHK(c->d_draw[1].ensure((size_t)n * 8)); FZCHK(c->d_draw[2].ensure((size_t)n * W * 8));
+        if (has_prior) FZCHK(c->d_draw[3].ensure((size_t)n * W * 8));
+        int64_t* d_nb = c->d_draw[0].as<int64_t>(); int64_t* d_nn = c->d_draw[1].as<int64_t>();
+        double* d_lnl = c->d_draw[2].as<double>(); double* d_lpr = has_prior ? c->d_draw[3].as<double>() : nullptr;
+        fz_prior_lerp pc; const fz_prior_lerp* prc = nullptr;
+        if (has_prior) {
+            pc = *pr; prc = &pc;
+            if (pr->frac) pc.frac = pr->frac + i0;
+            if (pr->rows) pc.rows = pr->rows + i0;
+            else if (pr->P != 1) {
+                if (pr->P != N) return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
+                pc.table = pr->table + i0 * M; pc.P = n;
+            }
+        }
+        FZCHK(fz_knn_search_fit_predict_prior_lerp(c, q + i0 * F, x + i0 * B, xe + i0 * B, xm + i0 * B, n, k, lp_norm, dub, o, nullptr, prc, d_nb,
+                                                   d_nn, nullptr, d_lnl, d_lpr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        FZCHK(da.run(c, i0, n, W, has_prior ? d_lpr : d_lnl, d_nb, d_nn, key0, key1, first, S));
+        if (neighbors) FZCHK(copy_out(c, neighbors + i0 * W, d_nb, (size_t)n * W * 8));
+        if (nnbr) FZCHK(copy_out(c, nnbr + i0, d_nn, (size_t)n * 8));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}

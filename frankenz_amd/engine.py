@@ -298,6 +298,47 @@ class Engine(object):
         check(self.lib.fz_predict_logwt(self.h, ptr(logwt), n, int(bool(is_log)), C.byref(kopts),
                                         ptr(pdfs), ptr(lmap), ptr(levid)))
 
+    # -- posterior draws over the model set (docs/draws.md; fz_draw.h) -----------
+    @staticmethod
+    def _draw_source(u, key):
+        """the uniforms of a draw call: the caller's ``u`` (N, S), or a two-word Philox ``key`` -> (u pointer, key0, key1)"""
+        if u is None and key is None:
+            raise ValueError("posterior draws need uniforms `u` or a Philox `key`")
+        k0, k1 = (0, 0) if key is None else (int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF)
+        return ptr(u), k0, k1
+
+    @staticmethod
+    def _prior_lerp_struct(prior):
+        """(table, P, rows[, frac]) -> fz_prior_lerp* (frac NULL: a plain ln table), or NULL"""
+        if prior is None:
+            return None
+        return C.byref(PriorLerp(ptr(prior[0]), int(prior[1]), ptr(prior[2]), ptr(prior[3]) if len(prior) == 4 else None))
+
+    def draw_logwt(self, logwt, S, idx, u=None, key=None, first=0, neighbors=None, nnbr=None, lmap=None, levid=None, n=None, W=None):
+        """fz_draw_logwt: ``S`` draws per row of ``logwt`` (n, W) into ``idx`` (n, S) int64; ``neighbors`` / ``nnbr``: the k-NN
+        form (valid entries per row, and the model index returned for each)"""
+        n = len(logwt) if n is None else n
+        W = logwt.shape[1] if W is None else W
+        up, k0, k1 = self._draw_source(u, key)
+        check(self.lib.fz_draw_logwt(self.h, ptr(logwt), int(n), int(W), ptr(neighbors), ptr(nnbr), up, k0, k1, int(first), int(S),
+                                     ptr(idx), ptr(lmap), ptr(levid)))
+
+    def fit_draw(self, x, xe, xm, opts, prior, S, idx, u=None, key=None, first=0, lmap=None, levid=None, n=None):
+        """fz_fit_draw: objects -> ``S`` draws each over the uploaded model set; ``prior`` as in ``fit_prior``"""
+        n = len(x) if n is None else n
+        up, k0, k1 = self._draw_source(u, key)
+        check(self.lib.fz_fit_draw(self.h, ptr(x), ptr(xe), ptr(xm), int(n), C.byref(opts), self._prior_lerp_struct(prior), up, k0, k1,
+                                   int(first), int(S), ptr(idx), ptr(lmap), ptr(levid)))
+
+    def knn_search_fit_draw(self, q, x, xe, xm, k, lp_norm, distance_upper_bound, opts, prior, S, idx, u=None, key=None, first=0,
+                            neighbors=None, nnbr=None, lmap=None, levid=None, n=None):
+        """fz_knn_search_fit_draw: the K searches, the subset likelihood and ``S`` draws (model indices) per object"""
+        n = len(x) if n is None else n
+        up, k0, k1 = self._draw_source(u, key)
+        check(self.lib.fz_knn_search_fit_draw(self.h, ptr(q), ptr(x), ptr(xe), ptr(xm), int(n), int(k), float(lp_norm),
+                                              float(distance_upper_bound), C.byref(opts), self._prior_lerp_struct(prior), up, k0, k1,
+                                              int(first), int(S), ptr(neighbors), ptr(nnbr), ptr(idx), ptr(lmap), ptr(levid)))
+
     # -- k-NN ------------------------------------------------------------
     def knn_upload_trees(self, feats, key=None):
         """``key``: the caller's content key of ``feats`` (``_digest``); an unchanged set is not sent (nor Morton-sorted) again"""

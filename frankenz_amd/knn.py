@@ -18,7 +18,7 @@ import sys
 import numpy as np
 
 from . import pdf as _pdf
-from .bruteforce import _check_lprob, _progress
+from .bruteforce import _check_lprob, _check_nsamples, _device_objects, _draw_outputs, _draw_uniforms, _progress
 from .engine import HostObjects, _digest, get_engine, kde_opts, like_opts, merge_kde_args, pinned_empty
 
 __all__ = ["NearestNeighbors"]
@@ -366,6 +366,90 @@ class NearestNeighbors():
             if track_scale:
                 res = res + (keep.fit_scale[i, :n], keep.fit_scale_err[i, :n])
             yield keep.neighbors[i, :n], n, res
+
+    # ------------------------------------------------------------------
+    def fit_sample(self, data, data_err, data_mask, Nsamples, lprob_func=None, rstate=None, k=20, eps=1e-3, lp_norm=2,
+                   distance_upper_bound=np.inf, lprob_args=None, lprob_kwargs=None, draws='device', return_gof=False,
+                   verbose=True, out=None, query_features=None):
+        """Extension (twin of ``BruteForce.fit_sample``; docs/draws.md): ``Nsamples`` posterior draws per object over its
+        neighbour subset; the values are MODEL indices (``-1`` throughout a row without a posterior).  Search arguments as in
+        ``fit_predict``.  ``rstate`` is consumed by the query draw first (knn.py:830-832), as today; the Philox key
+        (``draws='device'``, kept in ``philox_key``) or the uniforms (``draws='host'``) are drawn after it.  The ``fit_*`` arrays
+        are not filled (a user callable fills a scratch copy)."""
+        prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
+        S = _check_nsamples(Nsamples)
+        if rstate is None:
+            rstate = np.random
+        self._search_setup(k, eps, lp_norm, distance_upper_bound)
+        on_dev = hasattr(data, "data_ptr")
+        Ndata = int(data.shape[0]) if on_dev else len(data)
+        if host is not None:
+            if out is not None or on_dev or query_features is not None:
+                raise NotImplementedError("device arrays / `out=` / `query_features` need the built-in likelihood")
+            keep = copy.copy(self)
+            keep._host_run(host, data, data_err, data_mask, rstate, False)
+            u, key = _draw_uniforms(rstate, draws, Ndata, S)
+            self.philox_key = key
+            res = keep._draw_stored(keep.fit_lnprob, S, u, key)
+        else:
+            opts = like_opts(lprob_kwargs)
+            eng = self._engine()
+            if query_features is None:
+                if on_dev:
+                    raise NotImplementedError("device objects need `query_features` (the query draw is the host's)")
+                q = self._query_features(np.asarray(data), np.asarray(data_err), rstate)
+            else:
+                q = query_features if hasattr(query_features, "data_ptr") else np.ascontiguousarray(query_features, dtype=np.float64)
+                if tuple(q.shape) != (Ndata, self.NDIM):
+                    raise ValueError("`query_features` must have shape (Ndata, Nfilt) = (%d, %d)" % (Ndata, self.NDIM))
+            u, key = _draw_uniforms(rstate, draws, Ndata, S)
+            self.philox_key = key
+            if on_dev:
+                _device_objects(data, data_err, data_mask)
+                x, xe, xm, obj = data, data_err, data_mask, None
+            else:
+                obj = HostObjects(data, data_err, data_mask)
+                x, xe, xm = obj.x, obj.xe, obj.xm
+            res = _draw_outputs(eng, out, Ndata, S, like=data if on_dev else None)
+            if Ndata:
+                eng.knn_search_fit_draw(q, x, xe, xm, self.k, self.lp_norm, self.dbound, opts,
+                                        prior.chunk(0, Ndata, Ndata) if prior is not None else None, S, res[0], u=u, key=key,
+                                        lmap=res[1], levid=res[2], n=Ndata)
+            if obj is not None:
+                obj.writeback()
+        _progress(verbose, 'Sampling object', Ndata, Ndata)
+        if verbose:
+            sys.stderr.write('\n')
+            sys.stderr.flush()
+        return (res[0], (res[1], res[2])) if return_gof else res[0]
+
+    def _draw_stored(self, logwt, S, u, key):
+        """draws from padded ``(Ndata, K*k)`` rows beside the stored ``neighbors`` / ``Nneighbors``"""
+        Ndata = self.NDATA
+        W = self.neighbors.shape[1]
+        lw = np.ascontiguousarray(logwt, dtype=np.float64)
+        nb = np.ascontiguousarray(self.neighbors, dtype=np.int64)
+        nn = np.ascontiguousarray(self.Nneighbors, dtype=np.int64)
+        if lw.shape != (Ndata, W) or nb.shape != (Ndata, W) or nn.shape != (Ndata,):
+            raise ValueError("`logwt` has shape %s; expected (Ndata, K*k) = (%d, %d) like `neighbors`" % (lw.shape, Ndata, W))
+        eng = get_engine(self._device)
+        idx, lmap, levid = _draw_outputs(eng, None, Ndata, S)
+        if Ndata:
+            eng.draw_logwt(lw, S, idx, u=u, key=key, neighbors=nb, nnbr=nn, lmap=lmap, levid=levid, n=Ndata, W=W)
+        return idx, lmap, levid
+
+    def sample(self, Nsamples, logwt=None, rstate=None, draws='device', return_gof=False):
+        """Extension, the analogue of ``predict``: ``Nsamples`` draws (model indices) per object from the stored fits
+        (``fit_lnprob`` beside ``neighbors`` / ``Nneighbors``) or the given padded ``(Ndata, K*k)`` rows."""
+        S = _check_nsamples(Nsamples)
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None or getattr(self, "neighbors", None) is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        u, key = _draw_uniforms(rstate, draws, self.NDATA, S)
+        self.philox_key = key
+        idx, lmap, levid = self._draw_stored(logwt, S, u, key)
+        return (idx, (lmap, levid)) if return_gof else idx
 
     # ------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None,

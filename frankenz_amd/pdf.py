@@ -17,7 +17,7 @@ import numpy as np
 from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
-           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample"]
+           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels"]
 
 
 def _ndim_dtype(data_mask, models_mask):
@@ -199,6 +199,25 @@ class logprob_prior_lerp(object):
         prior = (self.table, self.P, self.rows[index:index + 1].copy(), self.frac[index:index + 1].copy())
         return _prior_one_object(self.M, prior, data, data_err, data_mask, models, models_err, models_mask, free_scale,
                                  ignore_model_err, dim_prior, ltol, return_scale, device)
+
+
+def sample_labels(idx, model_labels, model_label_errs=None, rstate=None):
+    """Labels of posterior draws (extension; ``BruteForce.fit_sample`` / ``.sample``, docs/draws.md): ``model_labels[idx]`` for any
+    label of the model set, afterwards, on the host; with ``model_label_errs`` AND ``rstate`` each value is jittered by
+    ``N(0, err)`` of its model; ``nan`` where ``idx == -1`` (a row without a posterior)."""
+    idx = np.asarray(idx)
+    labels = np.asarray(model_labels, dtype=np.float64)
+    if not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("`idx` must hold integer model indices")
+    if idx.size and (idx.min() < -1 or idx.max() >= len(labels)):
+        raise IndexError("`idx` holds an index outside [-1, %d)" % len(labels))
+    bad = idx < 0
+    safe = np.where(bad, 0, idx)
+    out = labels[safe]
+    if model_label_errs is not None and rstate is not None:
+        out = rstate.normal(out, np.asarray(model_label_errs, dtype=np.float64)[safe])
+    out[bad] = np.nan
+    return out
 
 
 def gaussian(mu, std, x):

@@ -481,6 +481,36 @@ int  fz_synphot_upload(fz_ctx* ctx, int64_t Nf, const int64_t* foff, const doubl
                        const double* ftab, int64_t Nt, const int64_t* toff, const double* tlw, const double* tasinh);
 int  fz_synphot(fz_ctx* ctx, int64_t Npair, const int64_t* tmpl, const double* z, const double* ln1pz, int32_t igm, double* out);
 
+/* ---- posterior draws over the model set (extension, no reference counterpart; docs/draws.md) ----
+ * For a row r[0..L) of ln-weights: w_j = exp(r_j - max r), cdf_j = w_0 + ... + w_j, tot = cdf_{L-1}; a draw with uniform u in [0, 1] is
+ * j = #{k : cdf_k <= u tot}, clipped to the last entry with w_j > 0 (the rule of fz_nz_assign).  A row that holds a nan, or whose max
+ * is not finite, gives -1 for every draw.  lmap / levid: the row's max and logsumexp (fp64).  The sums are formed in a fixed,
+ * segmented order (docs/draws.md): a draw is a function of (row, u) alone -- the same bits whatever the chunking (workspace limit),
+ * the object order, the number of objects in a call and the memory the arguments live in.
+ * Uniforms: u (N, S) from the caller, each checked to lie in [0, 1] before anything is drawn (-4); or u == NULL: Philox4x32-10 under
+ * (key0, key1) at the counter (first + i, s) for draw s of object i, the double formed as fz_nz_sweep forms it (`first`: the index of
+ * object 0 in the caller's whole array, so that a caller who splits a call gets the same draws).
+ * Limits (-5, before any launch): 1 <= S <= 65536 (FZ_DRAW_SMAX), rows of at most 2^20 entries (FZ_DRAW_LMAX); S < 1 is -4.
+ *
+ * fz_draw_logwt -- logwt (N, W) rows; neighbors (N, W) / nnbr (N) both NULL, or both given: only the first nnbr[i] entries of row i
+ *   count and the value returned for entry j is neighbors[i][j] (nnbr[i] outside [0, W]: -3).  idx (N, S) int64; lmap, levid (N) or NULL.
+ * fz_fit_draw -- objects -> draws with the built-in likelihood (every mode) and an optional ln-prior (prior->frac == NULL: a plain
+ *   ln table, else the interpolated form): per chunk the ln-likelihood plane of fz_fit (mode C: its final plane), + the prior, drawn
+ *   from in place; chunks sized from the workspace limit.  x, xe, xm are cleaned in place like fz_fit.
+ * fz_knn_search_fit_draw -- fz_knn_search_fit_predict_prior_lerp without the KDE half: the K searches, the subset likelihood (+ prior),
+ *   then draws from each object's padded ln-prob row; the values drawn are MODEL indices.  neighbors (N, K k) / nnbr (N): optional
+ *   outputs, as there. */
+int  fz_draw_logwt(fz_ctx* ctx, const double* logwt, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr,
+                   const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
+                   double* levid);
+int  fz_fit_draw(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* opts, const fz_prior_lerp* prior,
+                 const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
+                 double* levid);
+int  fz_knn_search_fit_draw(fz_ctx* ctx, const double* q, double* x, double* xe, double* xm, int64_t N, int32_t k, double lp_norm,
+                            double distance_upper_bound, const fz_like_opts* opts, const fz_prior_lerp* prior, const double* u,
+                            uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* neighbors, int64_t* nnbr, int64_t* idx,
+                            double* lmap, double* levid);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
