@@ -72,22 +72,62 @@ namespace fz {
 #ifndef FZ_HIST_REFRESH
 #define FZ_HIST_REFRESH 32     // steps between two updates of the candidate bar (and flushes of the fp32 partial sums)
 #endif
+#ifndef FZ_HIST_LEAN
+#define FZ_HIST_LEAN 1           // the settle's instruction stream without the register copies and the branch knot (0: as the compiler makes it)
+#endif
+// fma(a, b, c) as ONE three-address v_fma_f64 (same operands, same single rounding).  For the places where c is a constant that
+// lives in a register pair across the model loop: the compiler forms those as v_mov_b64 tmp, c + v_fmac_f64 tmp, a, b -- a copy per
+// use that computes nothing.  Not volatile: the scheduler stays free to move it.
+// (L: the instantiation takes the lean forms -- the screen form without segments; the segmented kernels keep the compiler's own)
+template <bool L>
+__device__ __forceinline__ double fma3(double a, double b, double c) {
+    if constexpr (L) { double d; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
+    else return fma(a, b, c);
+}
+// ... with b a wave-uniform constant in a scalar register pair (the one scalar operand a VOP3 takes)
+template <bool L>
+__device__ __forceinline__ double fma3_sb(double a, double b, double c) {
+    if constexpr (L) { double d; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c)); return d; }
+    else return fma(a, b, c);
+}
+// ... and fma(a, -0.5, c) with the inline constant
+template <bool L>
+__device__ __forceinline__ double fma3_mhalf(double a, double c) {
+    if constexpr (L) { double d; asm("v_fma_f64 %0, %1, -0.5, %2" : "=v"(d) : "v"(a), "v"(c)); return d; }
+    else return fma(a, -0.5, c);
+}
+// hi + ((n >> 8) << 20), the exponent insert of the table exponentials: mask + one v_lshl_add_u32 (the compiler's form of the
+// shifts is shift, mask, add); the same word for every n
+template <bool L>
+__device__ __forceinline__ int exp_insert(int hi, int n) {
+    if constexpr (L) { int r; asm("v_lshl_add_u32 %0, %1, 12, %2" : "=v"(r) : "v"(n & ~(FZ_HEXP_K - 1)), "v"(hi)); return r; }
+    else return hi + ((n >> 8) << 20);
+}
+// Three of exp_small_tab's constants as VALUES the caller holds (k_hist: made opaque once at the kernel's entry, two in scalar pairs, one
+// in a vector pair).  As literals the compiler shares their words with other constants of the kernel -- 256 / ln 2 and log2 e, ln 2 / 256
+// and ln 2, 1/6 and 1/24 differ in the high word only -- and rebuilds each pair from the shared word with a move at every use.
+struct ExpK {
+    double c1 = 369.3299304675746;             // 256 / ln 2
+    double c2 = -0.0027076061740622863;        // -ln 2 / 256
+    double c6 = 1.0 / 6.0;
+};
 // (NEGONLY: the caller's argument cannot exceed a few units -- the settle's -chi2 / 2 + const -- so only the lower clamp is applied)
-template <bool NEGONLY = false>
-__device__ __forceinline__ double exp_small_tab(double x, const double* __restrict__ tab) {
+template <bool NEGONLY = false, bool L = false>
+__device__ __forceinline__ double exp_small_tab(double x, const double* __restrict__ tab, const ExpK& ek = ExpK()) {
     const double MAGIC = 6755399441055744.0;                     // 1.5 * 2^52
     x = NEGONLY ? vmax_raw(x, -700.0) : vmin_raw(vmax_raw(x, -700.0), 700.0);      // also maps NaN -> -700
-    const double d = fma(x, 369.3299304675746, MAGIC);           // 256 / ln 2
-    const double r = fma(d - MAGIC, -0.0027076061740622863, x);  // ln 2 / 256
+    const double d = fma(x, ek.c1, MAGIC);
+    const double r = fma(d - MAGIC, ek.c2, x);
     const int n = __double2loint(d);
     const double t = tab[n & (FZ_HEXP_K - 1)];
-    double p = fma(r, 1.0 / 120.0, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
+    double p = fma3_sb<L>(r, 1.0 / 120.0, 1.0 / 24.0);
+    p = fma3<L>(p, r, ek.c6);
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
     const double v = t * p;                                      // in [1,2)
-    return __hiloint2double(__double2hiint(v) + ((n >> 8) << 20), __double2loint(v));
+    static_assert(FZ_HEXP_K == 256, "the exponent insert shifts n by log2 of the table's length");
+    return __hiloint2double(exp_insert<L>(__double2hiint(v), n), __double2loint(v));
 }
 
 // sqrt(r) for r > 0 from v_rsq_f64 (seed ~2^-24) with two coupled Newton steps on the ROOT itself (s += (r - s^2) y / 2: two
@@ -107,8 +147,8 @@ constexpr double hist_ln(double k) {
 }
 // w = L(chi2) / L(K) = (chi2 / K)^(K/2) exp(-(chi2 - K) / 2), all fp64: integer powers by multiplication,
 // the half power by a Newton-refined v_rsq_f64, one exp, no log
-template <int WP, bool SMALL = false>
-__device__ __forceinline__ double hist_exactw(double c2, const FastTabs& tb) {
+template <int WP, bool SMALL = false, bool L = false>
+__device__ __forceinline__ double hist_exactw(double c2, const FastTabs& tb, const ExpK& ek = ExpK()) {
     constexpr double K = (double)WP;
     const double r = c2 * (1.0 / K);
     double pw = 1.0;
@@ -138,7 +178,7 @@ __device__ __forceinline__ double hist_exactw(double c2, const FastTabs& tb) {
             q = (WP >> 1) ? q * sq : sq;
         }
         constexpr double EK = 0.5 * K - 0.5 * K * hist_ln(K);      // ln of K^(-K/2) e^(K/2)
-        return q * exp_small_tab<true>(fma(c2, -0.5, EK), tb.expt);
+        return q * exp_small_tab<true, L>(fma3_mhalf<L>(c2, EK), tb.expt, ek);
     }
     if constexpr (!SMALL && (WP >> 1) <= 3) {
         // the direct form: the same folding (so that the two forms build a pair's weight from the same factors: an object's ln-max then
@@ -269,11 +309,34 @@ struct HistState {
 // f_s = L_s(k_s) / e^LREF <= 1 (in the classifier: an offset of t), so every bound of the scheme (w <= 1, "w > wt_thresh is
 // sufficient") holds across patterns.  An ambiguous entry records its N_dim (Cand::pad) and is settled by the reference's rule
 // with its own ln-like.  Objects for which some pattern leaves too few bands for a bounded likelihood go to the exact sweep.
+//
+// HistArgs: the kernel's FIRST argument, by value -- it sits at offset 0 of the kernel-argument segment.  What the model loop reads
+// of it (the model records' pointers, the label words, the histogram offset) is taken from the argument as usual and lives in scalar
+// registers for the whole kernel.  Everything else -- the objects' pointers, the object map and order, the outputs, the KDE tables of
+// the finish -- is read by the per-object prologue and by the finish only: those two go through `hq()`, the argument segment's own
+// address behind an empty asm, so that the compiler cannot hoist the (scalar) loads to the kernel's entry and hold ~45 scalar
+// registers across a loop that never reads them.  (They were spilled into vector lanes, and the two vector registers that took
+// them pushed six of the loop's own into scratch.)
+template <class SRC>
+struct HistArgs {
+    SRC src;
+    KdeView kv;
+    int64_t N;
+    double* lmap; double* levid; double* pdfs;
+    const int* omap; int* redo; const int* order;
+    int normalize;
+};
 template <class SRC, int TW, int NW, bool EXACT, bool OBJK = (SRC::NB > 8), bool SEG = false>
-__global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __restrict__ kvp, int acc_stride, int64_t N, int M,
-                                                   double wt_thresh, int normalize, Cand* __restrict__ amb, int64_t cap,
-                                                   double* __restrict__ lmap, double* __restrict__ levid, double* __restrict__ pdfs,
-                                                   const int* __restrict__ omap, int* __restrict__ redo, const int* __restrict__ order) {
+__global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeView* __restrict__ kvp, int acc_stride, int M,
+                                                   double wt_thresh, Cand* __restrict__ amb, int64_t cap) {
+    constexpr bool LEAN = (FZ_HIST_LEAN == 1) && !SEG;                  // the lean settle and the arguments read at the point of use
+    auto hq = [&]() -> const HistArgs<SRC>& {
+        if constexpr (!LEAN) return a_;                                 // (the segmented kernels: as before, read once at the kernel's entry)
+        auto p = __builtin_amdgcn_kernarg_segment_ptr();           // (constant address space: scalar loads)
+        asm volatile("" : "+s"(p));
+        return *(const HistArgs<SRC>*)p;
+    };
+    const int64_t N = a_.N;                                             // (the launch's geometry below; the prologue and the finish ask hq())
     constexpr int TILE = hist_tile<SRC>(), RW = SRC::RW, TDR = RW * TILE, TD = TDR + TILE / 2, NT = NW * 64, OD = SRC::OBJ_DOUBLES;
     constexpr int WP = SRC::WPOW, BT = SRC::NB;
     static_assert(!OBJK || TW == 1, "per-object band counts: one object per wave");
@@ -284,7 +347,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
     int wpr = WP;
     double K = (double)WP;
     bool kok = true;                                                    // OBJK: the object's power is >= 1 (else: the exact sweep)
-    double lgq = src_.lp.lg_full;
+    double lgq = a_.src.lp.lg_full;
     constexpr int NOBJ = NW * TW;
     constexpr bool S2 = (FZ_HIST_SETTLE2 == 1) && !EXACT && SRC::NB <= 8 && SRC::RW <= 6 && SRC::LMODE == 1;      // two entries per lane and drain
     constexpr int CAP = S2 ? 192 : 128, DTHR = CAP - 64;                  // ring entries per object; drain from DTHR pending entries on
@@ -308,7 +371,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
     const int64_t nwaves = (int64_t)gridDim.x * NW, gw = (int64_t)blockIdx.x * NW + wave;
     const int64_t ngroups = (N + TW - 1) / TW, nrounds = (ngroups + nwaves - 1) / nwaves;
     const int ntiles = (M + TILE - 1) / TILE;
-    SRC src = src_;
+    SRC src = a_.src;
     src.tb = global_tabs();                                       // finish (log of the evidence, the ambiguous band): through the vector L1
     const FastTabs tb = src.tb;
     FastTabs tbx;                                                 // what hist_exactw reads in the model loop
@@ -317,7 +380,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         for (int k = tid; k < FZ_HEXP_K; k += NT) s_tabs[k] = FZ_EXP_TAB[k * (FZ_EXP_K / FZ_HEXP_K)];
         tbx.logt = nullptr; tbx.expt = s_tabs;
     }
-    const KdeView kv = *kvp;
+    // (the fields the kernel's form reads.  Without segments: pos and w0, from the argument.  The segmented kernels read theirs through
+    //  the uploaded copy as before: argument loads are all hoisted to the kernel's entry, and those kernels have no scalar register left)
+    const KdeView kv = [&]() { if constexpr (SEG) return *kvp; else return a_.kv; }();
     const int32_t* posw = SEG ? kv.mc_tag : kv.pos;
     const int w0 = SEG ? 0 : kv.w0;                                      // (a segment tag carries its histogram offset)
     double* objs = EXACT ? s_objs + wave * (TW * OD) : s_c2 + wave * (TW * CAP);
@@ -353,6 +418,8 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         else return src.lnl_of_chi2(c2);
     };
     double rK = 1.0;                                                    // SEG: 1 / K of the pattern in force
+    ExpK ek;
+    if constexpr (LEAN) asm volatile("" : "+s"(ek.c1), "+s"(ek.c2), "+v"(ek.c6));      // (opaque from here on: pairs of their own, see ExpK)
     auto exactw_tab = [&](double c2, const FastTabs& t, auto small) {
         if constexpr (SEG) {
             // (the common pattern -- every band observed on both sides -- has the compile-time power: the cheaper form, behind a wave-uniform
@@ -361,26 +428,28 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
             return hist_exactw_rt8<decltype(small)::value>(c2, wpr, K, rK, t);
         }
         else if constexpr (KRT) return hist_exactw_rt<decltype(small)::value>(c2, wpr, t);
-        else return hist_exactw<WP, decltype(small)::value>(c2, t);
+        else return hist_exactw<WP, decltype(small)::value, LEAN>(c2, t, ek);
     };
     double lref = uniform_d(lnl_c2(K));                           // ln L at the mode: the reference of every weight
     // object slot -> object: through `order` first (the launch's slots in the order of their expected cost, fz_hist_order.h: the screen
     // form without segments; every other form is compiled without the read), then through the launch's object map as before
-    auto obj_of = [&](int64_t s) -> int64_t {
+    auto obj_of = [&](const HistArgs<SRC>& h, int64_t s) -> int64_t {
         if constexpr (!EXACT && !SEG) {
-            if (order) { const int64_t q = (int64_t)order[s]; s = q < 0 ? 0 : (q < N ? q : N - 1); }      // (a permutation of [0, N): the clamp never acts)
+            if (h.order) { const int64_t q = (int64_t)h.order[s]; s = q < 0 ? 0 : (q < h.N ? q : h.N - 1); }      // (a permutation of [0, N): the clamp never acts)
         }
-        return omap ? (int64_t)omap[s] : s;
+        return h.omap ? (int64_t)h.omap[s] : s;
     };
 
     for (int64_t rnd = 0; rnd < nrounds; ++rnd) {
         const int64_t g = gw + rnd * nwaves;
         const bool work = g < ngroups;                            // wave-uniform
         const int64_t i0 = work ? g * TW : 0;
+        const HistArgs<SRC>& hp = hq();                             // the prologue's view of the arguments
+        [[maybe_unused]] const SRC& srcp = hp.src;                  // (same values as `src`; the objects' pointers are read here, per object)
 #pragma unroll
         for (int o = 0; o < TW; ++o) {
-            const int64_t os = i0 + o < N ? i0 + o : N - 1;
-            src.park_obj(obj_of(os), objs + o * OD, lane);
+            const int64_t os = i0 + o < hp.N ? i0 + o : hp.N - 1;
+            srcp.park_obj(obj_of(hp, os), objs + o * OD, lane);
         }
         for (int k = lane; k < TW * acc_stride; k += 64) rows[k] = 0.0;
         // SEG: state of the pattern in force (set by seg_switch below)
@@ -396,8 +465,8 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
             return fma(-0.5, c2, xl) - lg;
         };
         if constexpr (SEG) {
-            const int64_t os = i0 < N ? i0 : N - 1;
-            const int64_t oi = obj_of(os);
+            const int64_t os = i0 < hp.N ? i0 : hp.N - 1;
+            const int64_t oi = obj_of(hp, os);
             src.park_obj(oi, obj0, lane);
             if constexpr ((SRC::LMODE == 1 || SRC::LMODE == 2) && FZ_HIST_CHI2_2OP && !(SRC::LMODE == 2 && SRC::SAFE)) {
                 // the two-instruction chi2's units (s = sqrt(1 / var), xs = x s; below) once per object, not at every change of pattern
@@ -428,9 +497,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
             tmarg = uniform_f(tmarg);
         }
         if constexpr (OBJK && !SEG) {
-            const int64_t os = i0 < N ? i0 : N - 1;
-            const int64_t oi = obj_of(os);
-            const int nb = __builtin_amdgcn_readfirstlane(__popc(src.ov.bits[oi]));   // observed bands (pad bits are 0)
+            const int64_t os = i0 < hp.N ? i0 : hp.N - 1;
+            const int64_t oi = obj_of(hp, os);
+            const int nb = __builtin_amdgcn_readfirstlane(__popc(srcp.ov.bits[oi]));   // observed bands (pad bits are 0)
             wpr = nb - (SRC::LMODE == 2 ? 3 : 2);
             // power 0 (two observed bands; three with the free scale): L = e^{-chi2/2} / C, largest at chi2 = 0 -- still bounded by its
             // value at the mode, so the same scheme holds with K = 0.  Below that the likelihood is unbounded at chi2 -> 0: the sweep.
@@ -444,7 +513,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
             t_consts(K, hk23, T0c, tmarg);
             hk23 = uniform_f(hk23); T0c = uniform_f(T0c); tmarg = uniform_f(tmarg);
             tzero = wpr > 0 ? -INFINITY : T0c;
-            lgq = uniform_d(dp ? src.lp.lgtab[nb] : 0.5 * ((double)nb * FZ_LN2PI + src.ov.slv[oi]));
+            lgq = uniform_d(dp ? srcp.lp.lgtab[nb] : 0.5 * ((double)nb * FZ_LN2PI + srcp.ov.slv[oi]));
             lref = uniform_d(lnl_c2(K));
         }
         nl_stage_tile<SRC, TILE, NT, true>(src, posw, 0, tileA, tid, wave);
@@ -509,11 +578,24 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
             if constexpr (SEG) w *= fk;                           // (the pattern's mode value relative to the reference)
             hs.Sc[o] += w;
             hs.wmx[o] = vmax_raw(hs.wmx[o], w);
-            if (w > thr_def) unsafeAtomicAdd(&rows[o * acc_stride + tag + w0], w);
             // (every pair that can matter to the evidence comes through here, not only the few near the threshold: the ambiguous list
             //  takes those within wt_thresh of the best weight seen so far -- a superset of what the exact maximum will admit)
-            const bool am = act && !(w > thr_def) && w > hs.wamb[o];
-            const unsigned long long mask = __ballot(am);
+            bool am;
+            unsigned long long mask;
+            if constexpr (LEAN) {
+                // the two compares once, as lane masks: the stack runs under the first, the ambiguous entries are the second without the
+                // first (one scalar instruction, and one scalar test in front of the rare list code).  An inactive lane has w == 0 and
+                // the bar is >= 0, so it is in neither mask and `act` need not be asked again.
+                const bool stk = w > thr_def, bar = w > hs.wamb[o];
+                const unsigned long long mstk = __ballot(stk), mbar = __ballot(bar);
+                if (stk) unsafeAtomicAdd(&rows[o * acc_stride + tag + w0], w);
+                mask = mbar & ~mstk;
+                am = bar && !stk;
+            } else {
+                if (w > thr_def) unsafeAtomicAdd(&rows[o * acc_stride + tag + w0], w);
+                am = act && !(w > thr_def) && w > hs.wamb[o];
+                mask = __ballot(am);
+            }
             if (mask) {                                           // wave-uniform
                 const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
                 const int np = __builtin_popcountll(mask);
@@ -910,7 +992,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                                 if ((sw & 0x3fff) != segcur) {                     // a few dozen times per pass; nothing waits in the buffer
                                     if (mcw && segcur >= 0) {
                                         const int rko = kv.seg_rank[segcur];
-                                        if (kv.seg_rank[sw & 0x3fff] != rko) class_flush(rko, rows, pdfs + obj_of(i0) * kv.G);
+                                        if (kv.seg_rank[sw & 0x3fff] != rko) { const HistArgs<SRC>& hc = hq(); class_flush(rko, rows, hc.pdfs + obj_of(hc, i0) * kv.G); }
                                     }
                                     seg_switch(sw);
                                 }
@@ -968,8 +1050,19 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
         if (work) {
 #pragma unroll 1
             for (int o = 0; o < TW; ++o) {
-                if (i0 + o >= N) break;
-                const int64_t i = obj_of(i0 + o);
+                const HistArgs<SRC>& hf = hq();                     // the finish's view of the arguments
+                const KdeView& kvf = SEG ? kv : hf.kv;              // (segments: the copy the loop holds anyway)
+                if (i0 + o >= hf.N) break;
+                const int64_t i = obj_of(hf, i0 + o);
+                double* const pdfs = hf.pdfs;
+                // ln L of a chi2 and its value at the mode, the reference of every weight: with the compile-time power both follow from
+                // the arguments alone and are formed here, per object, instead of riding through the model loop in scalar registers
+                auto lnl_fin = [&](double c2) {
+                    if constexpr (KRT || !LEAN) return lnl_c2(c2);
+                    else return chi2_logpdf<true>(0.5 * WP, c2, hf.src.lp.lg_full, tb);
+                };
+                double lrf = lref;
+                if constexpr (!KRT && LEAN) lrf = uniform_d(lnl_fin(K));
                 double* row = rows + o * acc_stride;
                 double wbest_run = 0.0;
                 if constexpr (!EXACT) {
@@ -979,9 +1072,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                 }
                 // ln L of the best model = ln L(mode) + ln of its exact relative weight (4e-16 relative on the weight: 1e-16 on ln-max)
                 if constexpr (!EXACT) wbest_run = wave_max(hs.wmx[o]);
-                const double lbest = (wbest_run > 0.0) ? uniform_d(lref + log_pos(wbest_run, tb)) : -INFINITY;
+                const double lbest = (wbest_run > 0.0) ? uniform_d(lrf + log_pos(wbest_run, tb)) : -INFINITY;
                 const double stot = wave_sum(EXACT ? hs.S[o] : hs.Sc[o]);
-                const double le = lref + log_pos(stot, tb);
+                const double le = lrf + log_pos(stot, tb);
                 const float tm = EXACT ? 0.f : wave_maxf(hs.tmax[o]);
                 // no candidate at all, an evidence that is not a number, or a best weight so far below the mode that weights relative to
                 // the MODE leave the comfortable range (2^-400: every pair within the drop bar of it is still a normal number well above
@@ -1005,7 +1098,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                             l1 = in1 ? seg_lnl(e1.lnl, e1.pad & 0xff) : -INFINITY;
                             w1 = exp_neg(l1 - lref, tb);
                         } else {
-                            l1 = in1 ? lnl_c2(e1.lnl) : -INFINITY;
+                            l1 = in1 ? lnl_fin(e1.lnl) : -INFINITY;
                             w1 = exactw_tab(e1.lnl, tb, std::false_type{});
                         }
                         const bool s1 = in1 && (exp_neg(l1 - le, tb) > thr);   // strict
@@ -1030,9 +1123,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                     }
                 }
                 if (lane == 0) {
-                    if (lmap) lmap[i] = lbest;
-                    if (levid) levid[i] = le;
-                    if (!ok) redo[1 + atomicAdd(redo, 1)] = (int)i;
+                    if (hf.lmap) hf.lmap[i] = lbest;
+                    if (hf.levid) hf.levid[i] = le;
+                    if (!ok) hf.redo[1 + atomicAdd(hf.redo, 1)] = (int)i;
                 }
                 if constexpr (SEG) {
                     if (mcw) {
@@ -1043,12 +1136,13 @@ __global__ __launch_bounds__(NW * 64) void k_hist(SRC src_, const KdeView* __res
                         double tot = 0.0;
                         for (int tq = lane; tq < G; tq += 64) { const double vq = gout[tq] + row[tq]; row[tq] = vq; tot += vq; }
                         tot = wave_sum(tot);
+                        const int normalize = hf.normalize;
                         const double sc = normalize ? 1.0 / tot : 1.0 / stot;
                         for (int tq = lane; tq < G; tq += 64) gout[tq] = normalize ? row[tq] / tot : row[tq] * sc;
                         continue;
                     }
                 }
-                kde_finalize<true>(kv, row, ok, normalize, pdfs + i * kv.G, lane, ok ? 1.0 / stot : 1.0, true);
+                kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lane, ok ? 1.0 / stot : 1.0, true);
             }
         }
         __syncthreads();

@@ -448,8 +448,12 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
         if (dealt) FZCHK((fz_hist_order_build<SRC, OBJK>(c, src, n, M, ko->wt_thresh, fz_dbg_int("FZ_HIST_ORDER_STRIDE", 256),
                                                          fz_dbg_int("FZ_HIST_ORDER_OFFSET", 0), &order)));
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, src, c->d_kv.as<fz::KdeView>(), kv.acc_stride, n,
-                       (int)M, ko->wt_thresh, ko->normalize, c->d_cand.as<fz::Cand>(), acap, lmap, levid, pdfs, c->omap, c->d_redo.as<int>(), order);
+    // (the screen form without segments reads its KDE view from the argument itself; the uploaded copies serve the segmented kernels and the sweep)
+    fz::HistArgs<SRC> ha;
+    ha.src = src; ha.kv = kv; ha.N = n; ha.lmap = lmap; ha.levid = levid; ha.pdfs = pdfs;
+    ha.omap = c->omap; ha.redo = c->d_redo.as<int>(); ha.order = order; ha.normalize = ko->normalize;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), lds, c->stream, ha, c->d_kv.as<fz::KdeView>(), kv.acc_stride, (int)M, ko->wt_thresh,
+                       c->d_cand.as<fz::Cand>(), acap);
     if (sweep_ok) {
         SWS sws;
         if constexpr (std::is_same<SWS, SRC>::value) sws = src; else sws = *swsp;
