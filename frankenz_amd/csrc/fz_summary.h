@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "fz_interp.h"
+
 namespace fz {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
@@ -122,28 +124,7 @@ static __global__ __launch_bounds__(256) void k_gemm_f64(const double* __restric
         }
 }
 
-// ---- numpy.interp (compiled_base.c arr_interp) on device -----------------------------------
-// xp non-decreasing (plateaus allowed); j = last index with xp[j] <= x.
-template <class XP, class FP>
-__device__ __forceinline__ double interp1(double x, const XP& xp, const FP& fp, int n) {
-    if (x != x) return x;
-    if (x < xp(0)) return fp(0);
-    if (x > xp(n - 1)) return fp(n - 1);
-    int lo = 0, hi = n;                                  // first index with xp > x
-    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (x >= xp(mid)) lo = mid + 1; else hi = mid; }
-    const int j = lo - 1;
-    if (j >= n - 1) return fp(n - 1);
-    const double xj = xp(j), fj = fp(j);
-    if (xj == x) return fj;
-    const double fj1 = fp(j + 1), xj1 = xp(j + 1);
-    const double slope = (fj1 - fj) / (xj1 - xj);
-    double r = slope * (x - xj) + fj;
-    if (r != r) {
-        r = slope * (x - xj1) + fj1;
-        if (r != r && fj == fj1) r = fj;
-    }
-    return r;
-}
+// numpy.interp on device: interp1 of fz_interp.h
 
 // ---- per-object statistics: one wave per object ----------------------------------------------
 // stats rows (each of length N): 0-3 mean{value,std,conf,risk}, 4-7 median, 8-11 mode, 12-15 best,
@@ -166,7 +147,7 @@ static __global__ __launch_bounds__(256) void k_summarize(const double* __restri
     const int CH = (G + 63) / 64;                       // contiguous chunk per lane
     const int k0 = lane * CH, k1 = min(G, k0 + CH);
     // mean (pdf.py:988), mode (pdf.py:991: first maximum), chunk sums for the CDF (pdf.py:994)
-    double sp = 0.0, spg = 0.0, best = -INFINITY; int bidx = 0x7fffffff;
+    double sp = 0.0, spg = 0.0, best = -INFINITY; int bidx = k0;       // (a chunk of -inf only: its first point, as np.argmax)
     for (int k = k0; k < k1; ++k) {
         const double v = p[k];
         sp += v; spg = fma(v, grid[k], spg);
@@ -190,6 +171,10 @@ static __global__ __launch_bounds__(256) void k_summarize(const double* __restri
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const double v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
     double run = inc - sp;
+    {   // a chunk that holds a non-finite entry (sp - sp is NaN): the points before it still take the finite sum of the lanes below
+        const double below = __shfl_up(inc, 1, 64);
+        if (run != run) run = lane ? below : 0.0;
+    }
     for (int k = k0; k < k1; ++k) { run += p[k]; cdf[k] = run; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -207,7 +192,7 @@ static __global__ __launch_bounds__(256) void k_summarize(const double* __restri
     const double plow2 = __shfl(q, 0, 64), plow1 = __shfl(q, 1, 64), pmed = __shfl(q, 2, 64);
     const double phigh1 = __shfl(q, 3, 64), phigh2 = __shfl(q, 4, 64), pmc = __shfl(q, 5, 64);
     // "best": first minimum of the risk row (pdf.py:1025)
-    double rbest = INFINITY; int ridx = 0x7fffffff;
+    double rbest = INFINITY; int ridx = k0;                            // (a chunk of +inf only: its first point, as np.argmin)
     for (int k = k0; k < k1; ++k) {
         const double v = rk[k];
         if (v < rbest || (v != v && rbest == rbest)) { rbest = v; ridx = k; }
@@ -278,7 +263,7 @@ static __global__ __launch_bounds__(256) void k_resample(const double* __restric
     for (int k = lane; k < Gn; k += 64) {
         const double x = ng[k];
         double v;
-        if (x != x) v = x;
+        if (x != x && G > 1) v = x;                       // (one old node: its value at a NaN point too, numpy's one-node rule)
         else if (x < og[0]) v = left;                     // np.interp(left=..., right=...)
         else if (x > og[G - 1]) v = right;
         else v = interp1(x, OG, PV, G);

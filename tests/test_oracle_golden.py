@@ -328,6 +328,45 @@ def test_g10_pdfs_resample():
     eq(fo.pdfs_resample(g['pdfs_in'].copy(), g['grid'], g['new_grid'], renormalize=False, left=-1., right=2.), g['resampled_lr'])
 
 
+@pytest.mark.parametrize('kern', ['lorentz', 'tophat'])
+@pytest.mark.parametrize('ren', [True, False])
+def test_g21_pdfs_summarize_nonfinite_rows(ren, kern):
+    """golden g21 (tests/golden/make_golden_summary_edges.py): NaN entries at columns 0, 1, 33, 64 and at two columns, an all-NaN
+    row and an all-zero row on a 65-point grid.  NaNs where the reference has them, every other entry the same bits."""
+    g = load_golden('g21_summary_edges')
+    work = g['edge'].copy()
+    with np.errstate(all='ignore'):
+        res = fo.pdfs_summarize(work, g['grid'], renormalize=ren, urand=g['urand'], pkern=kern)
+    flat = np.array([a for grp in res[:5] for a in grp] + [res[5]])
+    tag = ('ren_' if ren else 'noren_') + kern
+    assert np.array_equal(flat, g[tag + '_stats'], equal_nan=True)
+    assert np.array_equal(work, g[tag + '_after'], equal_nan=True)
+    s, grid = g[tag + '_stats'], g['grid']
+    if not ren:           # what the golden pins: a partly NaN row keeps what lies before its NaN, the zero row sits on the grid's ends
+        assert np.isfinite(s[[4, 6, 14, 16, 17], 3]).all() and np.isnan(s[[0, 1, 2, 3, 5, 7, 18, 19], 3]).all()
+        assert s[8, 3] == grid[33] and (s[12, 1:7] == grid[0]).all()
+        assert s[0, 7] == 0. and (s[[4, 16, 17, 18, 19, 20], 7] == grid[-1]).all()
+    else:
+        assert np.isnan(np.delete(s[:, 1:8], [8, 12], axis=0)).all() and (s[[8, 12], 1:8] == grid[0]).all()
+
+
+def test_g21_pdfs_resample_nan_point_and_duplicate_node():
+    g = load_golden('g21_summary_edges')
+    same = lambda a, b: np.array_equal(a, b, equal_nan=True)
+    with np.errstate(all='ignore'):
+        assert same(fo.pdfs_resample(g['edge'].copy(), g['grid'], g['new_grid'], renormalize=False, left=-1., right=7.), g['resampled_lr'])
+        assert same(fo.pdfs_resample(g['edge'].copy(), g['grid'], g['new_grid']), g['resampled'])
+        assert same(fo.pdfs_resample(g['edge'].copy(), g['grid'], g['new_grid_finite']), g['resampled_finite'])
+        assert same(fo.pdfs_resample(g['dup_pdfs'].copy(), g['dup_grid'], g['dup_new_grid'], renormalize=False, left=-1., right=7.),
+                    g['dup_resampled_lr'])
+        assert same(fo.pdfs_resample(g['dup_pdfs'].copy(), g['dup_grid'], g['dup_new_grid']), g['dup_resampled'])
+    assert g['dup_resampled_lr'][0, 0] == 5. and np.isnan(g['resampled']).all() and np.isnan(g['dup_resampled'][1]).all()
+    # one old node: numpy gives its value at every point that is not off an end, a NaN point included
+    x = np.array([0.5, np.nan, 2., -1.])
+    assert same(fo.pdfs_resample(np.array([[3.], [0.]]), np.array([0.5]), x, renormalize=False, left=-1., right=7.),
+                np.array([np.interp(x, [0.5], r, left=-1., right=7.) for r in ([3.], [0.])]))
+
+
 NET_CASES = [('wt', dict(wt_thresh=1e-3), {}), ('cdf', dict(wt_thresh=None, cdf_thresh=0.05), {}),
              ('fixed', dict(wt_thresh=1e-2, track_scale=False), {'free_scale': False, 'ignore_model_err': True})]
 
