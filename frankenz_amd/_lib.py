@@ -134,6 +134,9 @@ ABI = {
                               _P, _P, _P]),
     "fz_knn_search_fit_draw": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _F64, _F64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _P,
                                          C.c_uint32, C.c_uint32, _I64, _I64, _P, _P, _P, _P, _P]),
+    "fz_mw_sweep": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, C.c_uint32, C.c_uint32, _I64, C.c_uint64, _P, _P]),
+    "fz_mw_dirichlet": (C.c_int, [_P, _P, _P, _I64, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P]),
+    "fz_mw_chain": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, C.c_uint32, C.c_uint32, _I64, C.c_uint64, _I32, _P, _P, _P]),
 }
 
 _lib = None

@@ -494,6 +494,14 @@ class BruteForce():
         return (idx, (lmap, levid)) if return_gof else idx
 
     # ------------------------------------------------------------------
+    def weight_sampler(self):
+        """Extension: a ``samplers.model_weight_sampler`` over the stored dense ``fit_lnlike`` rows, for hierarchical re-weighting of
+        the training set (docs/model_weights.md).  Dense rows are for model sets that fit as ``(Ndata, Nmodel)``."""
+        from .samplers import model_weight_sampler
+        if self.fit_lnlike is None:
+            raise ValueError("Fits have not been computed.")
+        return model_weight_sampler(self.fit_lnlike, device=self._device)
+
     def fit_predict(self, data, data_err, data_mask, model_labels, model_label_errs,
                     lprob_func=None, label_dict=None, label_grid=None, kde_args=None,
                     kde_kwargs=None, lprob_args=None, lprob_kwargs=None, return_gof=False,

@@ -19,6 +19,7 @@
 #include "fz_diag.h"
 #include "fz_synphot.h"
 #include "fz_draw.h"
+#include "fz_mw.h"
 
 using namespace fz;
 
@@ -1238,6 +1239,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_diag_host.inc"
 #include "fz_synphot_host.inc"
 #include "fz_draw_host.inc"
+#include "fz_mw_host.inc"
 
 #ifdef FZ_KM_STATS
 extern "C" int fz_debug_kmstats(unsigned long long* out, int reset) {

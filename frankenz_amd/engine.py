@@ -339,6 +339,24 @@ class Engine(object):
                                               float(distance_upper_bound), C.byref(opts), self._prior_lerp_struct(prior), up, k0, k1,
                                               int(first), int(S), ptr(neighbors), ptr(nnbr), ptr(idx), ptr(lmap), ptr(levid)))
 
+    # -- Gibbs over model weights (docs/model_weights.md; fz_mw.h) ----------------
+    def mw_sweep(self, rows, n, W, M, lnw, counts, u=None, key=None, first=0, sweep=0, neighbors=None, nnbr=None, assign=None):
+        """fz_mw_sweep: one draw per row of ``rows + lnw[neighbors]`` -> ``counts`` (M) int64 [and ``assign`` (n) int64]"""
+        up, k0, k1 = self._draw_source(u, key)
+        check(self.lib.fz_mw_sweep(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(lnw), up, k0, k1, int(first),
+                                   int(sweep), ptr(counts), ptr(assign)))
+
+    def mw_dirichlet(self, alpha, counts, M, key, sweep, pos, lnw):
+        """fz_mw_dirichlet: ``pos ~ Dirichlet(alpha + counts)`` and ``lnw = ln pos`` under the Philox ``key``"""
+        check(self.lib.fz_mw_dirichlet(self.h, ptr(alpha), ptr(counts), int(M), int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF,
+                                       int(sweep), ptr(pos), ptr(lnw)))
+
+    def mw_chain(self, rows, n, W, M, alpha, lnw, key, sweep0, nsweeps, counts, pos, first=0, neighbors=None, nnbr=None, counts_all=None):
+        """fz_mw_chain: ``nsweeps`` sweeps on device-resident rows; ``lnw`` in and out, ``counts`` / ``pos`` of the last one"""
+        check(self.lib.fz_mw_chain(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(alpha), ptr(lnw),
+                                   int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF, int(first), int(sweep0), int(nsweeps), ptr(counts),
+                                   ptr(pos), ptr(counts_all)))
+
     # -- k-NN ------------------------------------------------------------
     def knn_upload_trees(self, feats, key=None):
         """``key``: the caller's content key of ``feats`` (``_digest``); an unchanged set is not sent (nor Morton-sorted) again"""

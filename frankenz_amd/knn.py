@@ -451,6 +451,15 @@ class NearestNeighbors():
         idx, lmap, levid = self._draw_stored(logwt, S, u, key)
         return (idx, (lmap, levid)) if return_gof else idx
 
+    def weight_sampler(self):
+        """Extension: a ``samplers.model_weight_sampler`` over the stored fits -- the sparse rows ``fit_lnlike`` beside
+        ``neighbors`` / ``Nneighbors`` -- for hierarchical re-weighting of the training set (docs/model_weights.md)."""
+        from .samplers import model_weight_sampler
+        if self.fit_lnlike is None or getattr(self, "neighbors", None) is None:
+            raise ValueError("Fits have not been computed.")
+        return model_weight_sampler(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
+                                    device=self._device)
+
     # ------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None,
                 kde_args=None, kde_kwargs=None, return_gof=False, verbose=True):

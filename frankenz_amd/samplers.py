@@ -11,7 +11,7 @@ import numpy as np
 
 from .engine import get_engine
 
-__all__ = ["loglike_nz", "nz_assign", "stack_nz", "population_sampler", "hierarchical_sampler"]
+__all__ = ["loglike_nz", "nz_assign", "stack_nz", "population_sampler", "hierarchical_sampler", "model_weight_sampler"]
 
 _NZ_SEGMENT = 8            # saved samples of the population chain per library call (the state stays on the device in between)
 
@@ -146,6 +146,67 @@ def _philox_uniform(key, sweep, n):
     out = _philox4x32(key, ctr)
     a, b = out[:, 0] >> np.uint32(5), out[:, 1] >> np.uint32(6)
     return (a * 67108864.0 + b) / 9007199254740992.0
+
+
+_MW_KEY_XOR = 0x6D775F67      # second key word of the gamma draws (csrc/fz_mw.h: FZ_MW_KEY_XOR)
+_MW_TRIES = 64
+_MW_BOOST_SLOT = 128
+
+
+def _philox_gamma(key, sweep, shape, return_attempts=False):
+    """The ``Gamma(shape[j], 1)`` draws the device makes for models ``j = 0 .. len(shape)-1`` in sweep ``sweep`` under ``key``
+    (``fz_mw_dirichlet`` / ``fz_mw_chain``; the NumPy twin of csrc/fz_mw.h: mw_gamma).  Marsaglia & Tsang (2000) without the squeeze;
+    Philox4x32-10 under the key ``(key[0], key[1] ^ 0x6D775F67)`` -- a domain disjoint from the sweep's uniforms, which use ``key``
+    itself -- at the counter ``(j, slot, sweep lo, sweep hi)``: slot ``2 a`` gives attempt ``a`` its normal (Box-Muller of
+    ``u1 = 1 - U(words 0, 1)`` and ``u2 = U(words 2, 3)``), slot ``2 a + 1`` its acceptance uniform ``1 - U(words 0, 1)``, slot 128
+    the uniform of the shape + 1 boost for ``shape < 1``, applied in log space.  At most 64 attempts (``RuntimeError`` beyond).
+    ``return_attempts``: also the number of the attempt that was accepted."""
+    shape = np.ascontiguousarray(shape, dtype=np.float64)
+    n = len(shape)
+    if np.any(~np.isfinite(shape) | (shape <= 0.)):
+        raise ValueError("gamma shapes must be finite and positive")
+    gkey = (int(key[0]) & 0xFFFFFFFF, (int(key[1]) & 0xFFFFFFFF) ^ _MW_KEY_XOR)
+    sw = int(sweep)
+
+    def words(idx, slot):
+        ctr = np.stack([idx.astype(np.uint64), np.full(len(idx), slot, dtype=np.uint64), np.full(len(idx), sw & 0xFFFFFFFF, dtype=np.uint64),
+                        np.full(len(idx), sw >> 32, dtype=np.uint64)], axis=1)
+        return _philox4x32(gkey, ctr)
+
+    def u53(a, b):
+        return ((a >> np.uint32(5)) * 67108864.0 + (b >> np.uint32(6))) / 9007199254740992.0
+
+    boost = shape < 1.
+    a = np.where(boost, shape + 1., shape)
+    d = a - 1. / 3.
+    c = 1. / np.sqrt(9. * d)
+    g = np.full(n, -1.)
+    att = np.full(n, -1, dtype=np.int64)
+    todo = np.arange(n)
+    for t in range(_MW_TRIES):
+        if not len(todo):
+            break
+        o = words(todo, 2 * t)
+        u1, u2 = 1. - u53(o[:, 0], o[:, 1]), u53(o[:, 2], o[:, 3])
+        x = np.sqrt(-2. * np.log(u1)) * np.cos(6.283185307179586 * u2)
+        v1 = 1. + c[todo] * x
+        q = words(todo, 2 * t + 1)
+        ua = 1. - u53(q[:, 0], q[:, 1])
+        pos = v1 > 0.
+        v = np.where(pos, v1 * v1 * v1, 1.)
+        dd = d[todo]
+        acc = pos & (np.log(ua) < 0.5 * x * x + dd - dd * v + dd * np.log(v))
+        g[todo[acc]] = (dd * v)[acc]
+        att[todo[acc]] = t
+        todo = todo[~acc]
+    if len(todo):
+        raise RuntimeError("a gamma draw was not accepted within %d attempts" % _MW_TRIES)
+    if boost.any():
+        jb = np.nonzero(boost)[0]
+        o = words(jb, _MW_BOOST_SLOT)
+        ub = 1. - u53(o[:, 0], o[:, 1])
+        g[jb] = np.exp(np.log(g[jb]) + np.log(ub) / shape[jb])
+    return (g, att) if return_attempts else g
 
 
 class population_sampler(object):
@@ -389,3 +450,270 @@ class hierarchical_sampler(object):
                 sweep += 1
                 pos, ref_counts, lnpriorref, lnpost = one_sweep(pos, ref_counts, lnpriorref, sweep)
             yield pos, lnpost
+
+
+# ---- Gibbs over the weights of the training objects (docs/model_weights.md) -------------------------------------------------------
+def _is_torch(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "detach")
+
+
+def _mw_host(a):
+    """a host NumPy copy of an array that may live on the device (a DeviceArray or a tensor)"""
+    if isinstance(a, np.ndarray):
+        return a
+    if _is_torch(a):
+        return a.detach().cpu().numpy()
+    return a.numpy()
+
+
+def _mw_lnpost(counts, pos, alpha):
+    """multinomial ln-pmf of ``counts`` under ``pos`` (the counted objects are the trials) + Dirichlet ln-pdf of ``pos`` under
+    ``alpha``: the values of ``scipy.stats.multinomial.logpmf`` / ``dirichlet.logpdf``, written out so that an exact zero in ``pos``
+    gives an infinity and not an exception"""
+    from scipy.special import gammaln, xlogy
+    cnt = np.asarray(counts, dtype=np.float64)
+    lnlike = gammaln(cnt.sum() + 1.) - gammaln(cnt + 1.).sum() + xlogy(cnt, pos).sum()
+    lnprior = gammaln(alpha.sum()) - gammaln(alpha).sum() + xlogy(alpha - 1., pos).sum()
+    return lnlike + lnprior
+
+
+class model_weight_sampler(object):
+    """
+    Hierarchical re-weighting of a training set: Gibbs sampling of population weights ``w`` over the ``M`` training objects (models)
+    under a Dirichlet hyper-prior, given every object's ln-likelihood rows.  The law is the reference's ``hierarchical_sampler``
+    (samplers.py:311-535) on dense rows with the models in the place of the label grid: per sweep every object's assignment is
+    redrawn, ``j_i ~ exp(lnlike_ij) w_j``, and the weights are redrawn from ``Dirichlet(alpha + counts)``.  The realisation for a
+    seed is not the reference's.  ``ref_sample`` and ``beta`` are not taken: a reference sample of counts per training object has no
+    use here.  docs/model_weights.md.
+
+    ``lnlike``: ``(N, M)`` dense rows -- only for model sets that fit as ``(N, M)`` --, or ``(N, W)`` rows beside ``neighbors``
+    ``(N, W)`` int64, ``Nneighbors`` ``(N)`` and ``Nmodels`` (what ``NearestNeighbors.fit`` leaves; entries past ``Nneighbors[i]`` are
+    never read).  NumPy arrays are uploaded once, when the first chain starts; arrays already on the engine's GPU are used in place
+    (C-contiguous float64 rows and int64 tables) by every sweep -- the default start and ``logwt()`` alone read them back, see ``sample``.
+    Rows that do not fit the workspace limit or the device raise ``MemoryError`` with the bytes needed: nothing is spilled.
+
+    An object without a posterior under the current weights (a nan, a maximum that is not finite -- all of its neighbours at weight
+    0 included --, no neighbour) is left out of that sweep's counts.
+
+    ``draws='device'`` (default): every random number is made on the device by Philox4x32-10 under a key of two 32-bit words drawn
+    from ``rstate`` once per ``sample`` call (``philox_key``); a saved sample is ONE library call of ``thin`` sweeps, and only the
+    weights and the counts come back.  ``_philox_uniform(key, sweep, N)`` and ``_philox_gamma(key, sweep, alpha + counts)`` reproduce
+    them.  ``draws='host'``: per sweep ``rstate.rand(N)``, then ``rstate.dirichlet(alpha + counts)`` on the host -- reproducible from
+    the seed with NumPy alone.  ``sweep_counts`` holds the counts of every sweep of the last ``sample`` call.
+    """
+
+    def __init__(self, lnlike, neighbors=None, Nneighbors=None, Nmodels=None, device=None):
+        if (neighbors is None) != (Nneighbors is None):
+            raise ValueError("`neighbors` and `Nneighbors` come together")
+        if len(lnlike.shape) != 2:
+            raise ValueError("`lnlike` must have shape (Nobj, Nmodels) or (Nobj, K*k)")
+        N, W = (int(v) for v in lnlike.shape)
+        if neighbors is None:
+            if Nmodels is not None and int(Nmodels) != W:
+                raise ValueError("dense rows have one entry per model")
+            Nmodels = W
+        else:
+            if Nmodels is None:
+                raise ValueError("`Nmodels` must be given beside `neighbors`")
+            if tuple(neighbors.shape) != (N, W) or tuple(Nneighbors.shape) != (N,):
+                raise ValueError("`neighbors` must have the shape of `lnlike` and `Nneighbors` one entry per object")
+        if N < 1 or W < 1 or int(Nmodels) < 1:
+            raise ValueError("the sampler needs at least one object and one model")
+        self.lnlike, self.neighbors, self.Nneighbors = lnlike, neighbors, Nneighbors
+        self.NOBJ, self.W, self.NMODEL = N, W, int(Nmodels)
+        self.device = device
+        self.samples = []
+        self.samples_lnp = []
+        self.sweep_counts = []
+        self.philox_key = None
+        self._dev = None
+
+    def reset(self):
+        """Re-initialize the sampler."""
+        self.samples = []
+        self.samples_lnp = []
+
+    @property
+    def results(self):
+        """Return samples: ``(samples (Niter, M), samples_lnp (Niter))``."""
+        return np.array(self.samples), np.array(self.samples_lnp)
+
+    def _resident(self, eng):
+        """the rows (and neighbour tables) on the engine's GPU: uploaded once, or the caller's device arrays themselves"""
+        if self._dev is not None:
+            return self._dev
+        # only what is UPLOADED needs room: arrays already on the device are used where they lie
+        parts = [a for a in (self.lnlike, self.neighbors, self.Nneighbors) if isinstance(a, np.ndarray)]
+        need = sum(int(a.size) * 8 for a in parts)
+        if need > eng.workspace_limit():
+            raise MemoryError("model_weight_sampler: the rows need %d bytes of device memory, the workspace limit is %d (nothing is "
+                              "spilled)" % (need, eng.workspace_limit()))
+
+        def put(a, dt):
+            if a is None:
+                return None
+            if isinstance(a, np.ndarray):
+                try:
+                    return eng.device_array(np.ascontiguousarray(a, dtype=dt))
+                except MemoryError:
+                    raise MemoryError("model_weight_sampler: the rows need %d bytes of device memory" % need)
+            if not hasattr(a, "data_ptr"):
+                raise TypeError("rows must be NumPy arrays or arrays on the GPU")
+            # a device array is read as raw C-contiguous memory of 8-byte items: anything else is refused
+            if hasattr(a, "element_size") and a.element_size() != 8:
+                raise TypeError("device rows must be float64 and device neighbour tables int64")
+            kind = getattr(a, "dtype", None)
+            if kind is not None and not str(kind).endswith(np.dtype(dt).name):
+                raise TypeError("a device array of dtype %s where %s is needed" % (kind, np.dtype(dt).name))
+            if hasattr(a, "is_contiguous") and not a.is_contiguous():
+                raise ValueError("device arrays must be C-contiguous (a strided view would be read as raw memory)")
+            return a
+
+        self._dev = (put(self.lnlike, np.float64), put(self.neighbors, np.int64), put(self.Nneighbors, np.int64))
+        return self._dev
+
+    def _stack_start(self):
+        """the analogue of ``stack_nz``: ``pos_j`` proportional to ``sum_i exp(r_ij - logsumexp_j' r_ij')``, a scatter-add of the
+        normalised rows (once per chain, on the host)"""
+        from scipy.special import logsumexp
+        M = self.NMODEL
+        r = np.asarray(_mw_host(self.lnlike), dtype=np.float64)
+        pos = np.zeros(M)
+        step = max(1, (1 << 24) // self.W)
+        nb = None if self.neighbors is None else _mw_host(self.neighbors)
+        nn = None if self.neighbors is None else np.asarray(_mw_host(self.Nneighbors))
+        for lo in range(0, self.NOBJ, step):
+            rr = r[lo:lo + step]
+            if nb is not None:
+                valid = np.arange(self.W)[None, :] < nn[lo:lo + step, None]
+                rr = np.where(valid, rr, -np.inf)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                p = np.exp(rr - logsumexp(rr, axis=1, keepdims=True))
+            p[~np.isfinite(p).all(axis=1)] = 0.
+            if nb is None:
+                pos += p.sum(axis=0)
+            else:
+                np.add.at(pos, np.where(valid, nb[lo:lo + step], 0).ravel(), np.where(valid, p, 0.).ravel())
+        if not pos.sum() > 0.:
+            raise ValueError("no object has a posterior over the models: give `pos_init`")
+        return pos / pos.sum()
+
+    def run_mcmc(self, Niter, alpha=None, pos_init=None, thin=5, rstate=None, verbose=True, draws='device'):
+        """Sample the weights using Gibbs MCMC: ``Niter`` saved samples of ``thin`` sweeps each, appended to ``samples`` /
+        ``samples_lnp``.  As in ``hierarchical_sampler``, a second call without ``pos_init`` restarts from the stacked rows."""
+        for i, (x, lnp) in enumerate(self.sample(Niter, alpha=alpha, pos_init=pos_init, thin=thin, rstate=rstate, draws=draws)):
+            self.samples.append(np.array(x))
+            self.samples_lnp.append(lnp)
+            if verbose:
+                sys.stderr.write('\r Sample {:d}/{:d} [lnpost = {:6.3f}]      '.format(i + 1, Niter, lnp))
+                sys.stderr.flush()
+
+    def sample(self, Niter, alpha=None, pos_init=None, thin=5, rstate=None, draws='device'):
+        """Generator over the saved samples ``(pos, lnpost)``: ``pos`` the weights (M), ``lnpost`` the multinomial ln-pmf of the
+        sweep's counts under ``pos`` plus the Dirichlet ln-pdf of ``pos`` under ``alpha``.  One sweep runs ahead of the loop, as in
+        the reference's sampler.  ``pos_init=None`` starts from the stacked normalised rows, which are formed ON THE HOST once per
+        ``sample`` call: rows (and neighbour tables) that live on the device are copied back for it, all N x W of them (about
+        8 GB at 1e6 objects and ``K k`` = 500) -- give ``pos_init`` (a flat ``np.full(M, 1. / M)`` will do) to keep device-resident
+        rows where they are.  A start with a negative or non-finite entry, or an ``alpha`` that is not positive and finite,
+        raises ``ValueError``."""
+        if draws not in ('device', 'host'):
+            raise ValueError("`draws` must be 'device' or 'host'")
+        N, W, M = self.NOBJ, self.W, self.NMODEL
+        Niter, thin = int(Niter), int(thin)
+        if thin < 1:
+            raise ValueError("`thin` must be at least 1")
+        alpha = np.ones(M) if alpha is None else np.ascontiguousarray(alpha, dtype=np.float64)
+        if alpha.shape != (M,) or np.any(~np.isfinite(alpha) | (alpha <= 0.)):
+            raise ValueError("`alpha` must hold one finite positive entry per model")
+        pos = self._stack_start() if pos_init is None else _check_start(pos_init, M)
+        if rstate is None:
+            rstate = np.random
+        eng = get_engine(self.device)
+        d_rows, d_nb, d_nn = self._resident(eng)
+        with np.errstate(divide='ignore'):
+            lnw = np.log(pos)
+        self.sweep_counts = []
+        counts = np.zeros(M, dtype=np.int64)
+        if draws == 'host':
+            self.philox_key = None
+
+            def sweep():
+                eng.mw_sweep(d_rows, N, W, M, lnw, counts, u=np.ascontiguousarray(rstate.rand(N)), neighbors=d_nb, nnbr=d_nn)
+                self.sweep_counts.append(counts.copy())
+                p = rstate.dirichlet(alpha + counts)
+                with np.errstate(divide='ignore'):
+                    return p, np.log(p)
+
+            pos, lnw = sweep()
+            for i in range(Niter):
+                for j in range(thin):
+                    pos, lnw = sweep()
+                yield pos, _mw_lnpost(self.sweep_counts[-1], pos, alpha)
+            return
+        key = rstate.randint(0, 2**32, size=2, dtype=np.uint32)
+        self.philox_key = key
+        d_alpha, d_lnw = eng.device_array(alpha), eng.device_array(lnw)
+        pos = np.empty(M)
+        eng.mw_chain(d_rows, N, W, M, d_alpha, d_lnw, key, 0, 1, counts, pos, neighbors=d_nb, nnbr=d_nn)
+        self.sweep_counts.append(counts.copy())
+        for i in range(Niter):
+            call = np.empty((thin, M), dtype=np.int64)
+            eng.mw_chain(d_rows, N, W, M, d_alpha, d_lnw, key, 1 + i * thin, thin, counts, pos, neighbors=d_nb, nnbr=d_nn, counts_all=call)
+            self.sweep_counts.extend(call)
+            yield pos.copy(), _mw_lnpost(counts, pos, alpha)
+
+    # ---- what the weights are for -------------------------------------------------------------------------------------------------
+    def _weights(self, w):
+        if w is None:
+            if not len(self.samples):
+                raise ValueError("no samples yet: run the sampler or give `w`")
+            w = np.mean(self.samples, axis=0)
+        w = np.asarray(w, dtype=np.float64)
+        if w.shape[-1] != self.NMODEL:
+            raise ValueError("`w` must have one entry per model")
+        return w
+
+    def logwt(self, w=None):
+        """``(N, W)`` rows ``lnlike + ln w[neighbors]`` (dense: ``lnlike + ln w``): the objects' ln-posterior rows under the inferred
+        population, for the fitter's ``predict(logwt=)`` / ``sample(logwt=)``.  ``w`` defaults to the mean of the samples.  Entries
+        past ``Nneighbors[i]`` keep the row's own padding.  NumPy, or torch when the rows are tensors."""
+        w = self._weights(w)
+        if w.ndim != 1:
+            raise ValueError("`w` must be one weight vector")
+        with np.errstate(divide='ignore'):
+            lnw = np.log(w)
+        if _is_torch(self.lnlike):
+            import torch
+            r = self.lnlike
+            t = torch.as_tensor(lnw, dtype=r.dtype, device=r.device)
+            if self.neighbors is None:
+                return r + t[None, :]
+            nb, nn = torch.as_tensor(self.neighbors, device=r.device), torch.as_tensor(self.Nneighbors, device=r.device)
+            valid = torch.arange(self.W, device=r.device)[None, :] < nn[:, None]
+            return torch.where(valid, r + t[torch.where(valid, nb, torch.zeros_like(nb))], r)
+        r = np.asarray(_mw_host(self.lnlike), dtype=np.float64)
+        if self.neighbors is None:
+            return r + lnw[None, :]
+        nb, nn = _mw_host(self.neighbors), np.asarray(_mw_host(self.Nneighbors))
+        valid = np.arange(self.W)[None, :] < nn[:, None]
+        with np.errstate(invalid='ignore'):
+            return np.where(valid, r + lnw[np.where(valid, nb, 0)], r)
+
+    def population_pdfs(self, model_labels, model_label_errs, label_dict=None, label_grid=None, kde_kwargs=None, w=None):
+        """The weight samples as population distributions of a label: ``(Niter, G)`` n(label) samples, row ``s`` the KDE of the
+        models' labels weighted by ``w[s]`` (the reference's ``gauss_kde_dict`` / ``gauss_kde`` with ``y_wt = w[s]``, normalised
+        unless ``kde_kwargs`` says otherwise).  ``w`` defaults to all the samples.  The KDE clips weights below ``wt_thresh`` (1e-3)
+        of the largest: pass ``kde_kwargs={'wt_thresh': 0}`` if no weight is to be clipped."""
+        from .engine import kde_opts
+        if label_dict is None and label_grid is None:
+            raise ValueError("`label_dict` or `label_grid` must be specified.")
+        w = np.array(self.samples) if w is None else self._weights(w)
+        w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
+        if w.shape[1] != self.NMODEL or len(model_labels) != self.NMODEL:
+            raise ValueError("`w` and the labels must have one entry per model")
+        eng = get_engine(self.device)
+        Nx = eng.set_labels(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs)
+        pdfs = np.empty((len(w), Nx))
+        if len(w):
+            eng.predict_logwt(w, kde_opts(kde_kwargs), pdfs, is_log=False, n=len(w))
+        return pdfs

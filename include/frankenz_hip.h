@@ -511,6 +511,35 @@ int  fz_knn_search_fit_draw(fz_ctx* ctx, const double* q, double* x, double* xe,
                             uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* neighbors, int64_t* nnbr, int64_t* idx,
                             double* lmap, double* levid);
 
+/* ---- hierarchical re-weighting of the training set: Gibbs over model weights (extension; docs/model_weights.md) ----
+ * The law of the reference's hierarchical_sampler (samplers.py:311-535) with the M training objects in the place of the label grid.
+ * One sweep: per object the row t_ij = rows_ij + lnw[nbr_ij] (one fp64 add; dense rows: nbr_ij = j, W == M) and ONE posterior draw
+ * from it, exactly the draw of fz_draw_logwt on that row; counts_j = objects assigned to j; a row without a posterior (a nan, a max
+ * that is not finite -- all its neighbours at weight 0 included --, nnbr[i] == 0) is left out of the counts and gets assign = -1.
+ * Then g_j ~ Gamma(alpha_j + counts_j, 1), pos = g / sum(g), lnw = log(g) - log(sum(g)) (g_j = 0: lnw_j = -inf).
+ * Random numbers: Philox4x32-10.  The sweep's uniform of object i is the one of fz_nz_sweep under (key0, key1) at the counter
+ * (first + i, sweep).  The gamma draws use the key (key0, key1 ^ 0x6D775F67) and the counter (j, slot, sweep lo, sweep hi): slot 2a
+ * the normal of attempt a (Box-Muller of the two doubles of the four words), slot 2a + 1 its acceptance uniform, slot 128 the
+ * uniform of the shape + 1 boost (Marsaglia-Tsang; at most 64 attempts, else -7).  The sum of g is formed in one fixed order.
+ * Refusals: W > 2^20 (FZ_DRAW_LMAX) or M >= 2^31 (FZ_MW_MMAX): -5 before any launch; a neighbour index outside [0, M) within
+ * nnbr[i], or nnbr[i] outside [0, W]: -3 (the index is not used to read anything; counts are then not to be used); alpha_j <= 0 or
+ * not finite: -4; a caller's uniform outside [0, 1]: -4.
+ *
+ * fz_mw_sweep -- one sweep's assignments.  rows (N, W), neighbors (N, W) / nnbr (N) (both NULL: dense), u (N) or NULL (Philox),
+ *   assign (N) or NULL: host or device, staged in chunks from the workspace limit; lnw (M), counts (M, int64; zeroed by the call).
+ * fz_mw_dirichlet -- the weights' step: alpha (M), counts (M) -> pos (M), lnw (M); host or device.
+ * fz_mw_chain -- nsweeps sweeps (numbers sweep0, sweep0 + 1, ...) back to back without a host synchronisation inside; rows, neighbors
+ *   and nnbr must be device arrays.  lnw (M) in and out; counts (M) and pos (M) of the last sweep; counts_all (nsweeps, M) or NULL:
+ *   the counts of every sweep.  Bit for bit nsweeps calls of fz_mw_sweep (u == NULL) + fz_mw_dirichlet. */
+int  fz_mw_sweep(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                 const double* lnw, const double* u, uint32_t key0, uint32_t key1, int64_t first, uint64_t sweep, int64_t* counts,
+                 int64_t* assign);
+int  fz_mw_dirichlet(fz_ctx* ctx, const double* alpha, const int64_t* counts, int64_t M, uint32_t key0, uint32_t key1, uint64_t sweep,
+                     double* pos, double* lnw);
+int  fz_mw_chain(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                 const double* alpha, double* lnw, uint32_t key0, uint32_t key1, int64_t first, uint64_t sweep0, int32_t nsweeps,
+                 int64_t* counts, double* pos, int64_t* counts_all);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
