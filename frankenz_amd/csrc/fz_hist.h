@@ -75,6 +75,10 @@ namespace fz {
 #ifndef FZ_HIST_LEAN
 #define FZ_HIST_LEAN 1           // the settle's instruction stream without the register copies and the branch knot (0: as the compiler makes it)
 #endif
+#ifndef FZ_HIST_AHEAD
+#define FZ_HIST_AHEAD 1          // the lean screen form with band-constant errors and compile-time band counts (the headline's, at every band count):
+                                 // the next record's LDS reads pinned in front of the chi2 (0: where the compiler's scheduler puts them)
+#endif
 // fma(a, b, c) as ONE three-address v_fma_f64 (same operands, same single rounding).  For the places where c is a constant that
 // lives in a register pair across the model loop: the compiler forms those as v_mov_b64 tmp, c + v_fmac_f64 tmp, a, b -- a copy per
 // use that computes nothing.  Not volatile: the scheduler stays free to move it.
@@ -330,6 +334,9 @@ template <class SRC, int TW, int NW, bool EXACT, bool OBJK = (SRC::NB > 8), bool
 __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeView* __restrict__ kvp, int acc_stride, int M,
                                                    double wt_thresh, Cand* __restrict__ amb, int64_t cap) {
     constexpr bool LEAN = (FZ_HIST_LEAN == 1) && !SEG;                  // the lean settle and the arguments read at the point of use
+    // FZ_HIST_AHEAD: narrow records (band-constant errors) and compile-time band counts only.  The pinned reads of a 10-double record cost the
+    // per-model-error form 16 B of scratch; the per-object band-count form was 1.2 % slower in the one build that had it (docs/k_hist.md)
+    constexpr bool AHD = (FZ_HIST_AHEAD == 1) && LEAN && !EXACT && !(FZ_HIST_SETTLE2 == 1) && !OBJK && SRC::RW <= 6;
     auto hq = [&]() -> const HistArgs<SRC>& {
         if constexpr (!LEAN) return a_;                                 // (the segmented kernels: as before, read once at the kernel's entry)
         auto p = __builtin_amdgcn_kernarg_segment_ptr();           // (constant address space: scalar loads)
@@ -971,6 +978,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                                 tagn[q] = tags[(st + MP + q) * 64 + lane];
                             }
                         }
+                        // AHD: the reads above stay in front of the chi2 (left to itself the scheduler sinks them below it, and the next step
+                        // opens with a wait for a record requested a dozen instructions earlier)
+                        if constexpr (AHD && PF) __builtin_amdgcn_sched_barrier(0);
                         step_body(m, ptag, st, t, tailc, std::false_type{}, false);
                     }
                 } else {
