@@ -79,6 +79,16 @@ namespace fz {
 #define FZ_HIST_AHEAD 1          // the lean screen form with band-constant errors and compile-time band counts (the headline's, at every band count):
                                  // the next record's LDS reads pinned in front of the chi2 (0: where the compiler's scheduler puts them)
 #endif
+// The two below are for the instantiations that have FZ_HIST_AHEAD (AHD in k_hist); they move waits and change no arithmetic, no operand and
+// no order of operations (docs/k_hist.md, "Waits for what the step consumes").  0: the code without them.
+#ifndef FZ_HIST_WAIT_EARLY
+#define FZ_HIST_WAIT_EARLY 0     // 1: a full LDS wait between the classifier and the append: there only the next record's reads are outstanding, so
+                                 // the next step need not open with a wait that also covers this step's ring stores and histogram adds.  Built
+#endif                           // and measured: 0.5 % alone, inside the margin, and nothing on top of FZ_HIST_SEAM -- compiled out
+#ifndef FZ_HIST_SEAM
+#define FZ_HIST_SEAM 1           // the tile's wait + barrier stand in front of its LAST group, whose prefetch slot reads the first group of the
+                                 // NEXT tile: the next tile starts from registers instead of with an exposed LDS read behind a barrier
+#endif
 // fma(a, b, c) as ONE three-address v_fma_f64 (same operands, same single rounding).  For the places where c is a constant that
 // lives in a register pair across the model loop: the compiler forms those as v_mov_b64 tmp, c + v_fmac_f64 tmp, a, b -- a copy per
 // use that computes nothing.  Not volatile: the scheduler stays free to move it.
@@ -337,6 +347,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     // FZ_HIST_AHEAD: narrow records (band-constant errors) and compile-time band counts only.  The pinned reads of a 10-double record cost the
     // per-model-error form 16 B of scratch; the per-object band-count form was 1.2 % slower in the one build that had it (docs/k_hist.md)
     constexpr bool AHD = (FZ_HIST_AHEAD == 1) && LEAN && !EXACT && !(FZ_HIST_SETTLE2 == 1) && !OBJK && SRC::RW <= 6;
+    // FZ_HIST_WAIT_EARLY / FZ_HIST_SEAM: the same instantiations (no segments there: every tile is "pure")
+    constexpr bool WE = (FZ_HIST_WAIT_EARLY == 1) && AHD;
+    constexpr bool SEAM = (FZ_HIST_SEAM == 1) && AHD && hist_prefetch<SRC>() && (FZ_HIST_STAGE_LATE == 1);
     auto hq = [&]() -> const HistArgs<SRC>& {
         if constexpr (!LEAN) return a_;                                 // (the segmented kernels: as before, read once at the kernel's entry)
         auto p = __builtin_amdgcn_kernarg_segment_ptr();           // (constant address space: scalar loads)
@@ -523,7 +536,11 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
             lgq = uniform_d(dp ? srcp.lp.lgtab[nb] : 0.5 * ((double)nb * FZ_LN2PI + srcp.ov.slv[oi]));
             lref = uniform_d(lnl_c2(K));
         }
-        nl_stage_tile<SRC, TILE, NT, true>(src, posw, 0, tileA, tid, wave);
+        // (SEAM: the thread's index behind an empty asm, per round -- the three global addresses of this copy are then formed here, once
+        //  per round, instead of at the kernel's entry: held across the model loop they are the registers the carried record needs)
+        int tid0 = tid;
+        if constexpr (SEAM) asm volatile("" : "+v"(tid0));
+        nl_stage_tile<SRC, TILE, NT, true>(src, posw, 0, tileA, tid0, wave);
         __syncthreads();
         // the wave's objects stay in VGPRs for the whole model loop (an LDS broadcast read: the compiler
         // cannot tell that they are wave-uniform and keeps them out of the scalar file)
@@ -616,15 +633,15 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
             }
         };
         // settle the LAST (up to) 64 entries of object o's buffer with all lanes (their order does not matter: nothing has to move)
-        auto drain = [&](int o, auto badc) {
+        auto drain = [&](int o, auto badc, int ln) {
             if constexpr (S2) {
                 // the last (up to) 128 entries, two per lane: the two exact weights are independent chains in one basic block (a single
                 // chain of ~35 dependent fp64 operations left the vector pipe idle a third of the time at four waves per SIMD)
                 const int n = hs.pend[o] < 128 ? hs.pend[o] : 128;
                 const int rest = hs.pend[o] - n;
-                const double ca = rc2[o * CAP + rest + lane], cb = rc2[o * CAP + rest + 64 + lane];
-                const int ta = (int)rtag[o * CAP + rest + lane], tb2 = (int)rtag[o * CAP + rest + 64 + lane];
-                const bool aa = lane < n, ab = lane + 64 < n;
+                const double ca = rc2[o * CAP + rest + ln], cb = rc2[o * CAP + rest + 64 + ln];
+                const int ta = (int)rtag[o * CAP + rest + ln], tb2 = (int)rtag[o * CAP + rest + 64 + ln];
+                const bool aa = ln < n, ab = ln + 64 < n;
                 double wa, wb;
                 if (decltype(badc)::value && segbad) {
                     wa = aa ? exp_clamped(seg_lnl(ca, ndcur) - lref, tb) : 0.0; wb = ab ? exp_clamped(seg_lnl(cb, ndcur) - lref, tb) : 0.0;
@@ -654,9 +671,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
             }
             const int n = hs.pend[o] < 64 ? hs.pend[o] : 64;
             const int rest = hs.pend[o] - n;                      // < 64
-            double c2 = rc2[o * CAP + rest + lane];
-            int tag = (int)rtag[o * CAP + rest + lane];
-            const bool act = lane < n;
+            double c2 = rc2[o * CAP + rest + ln];
+            int tag = (int)rtag[o * CAP + rest + ln];
+            const bool act = ln < n;
             settle(o, act, c2, tag, badc);
             hs.pend[o] = SEG ? __builtin_amdgcn_readfirstlane(rest) : rest;
         };
@@ -906,6 +923,13 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                             const bool le = tl[q][o] <= hs.tthr[o];
                             const bool c = !le;
                             asm("v_max_f32 %0, %1, %2" : "=v"(hs.tmax[o]) : "v"(hs.tmax[o]), "v"(tl[q][o]));   // (a nan operand yields the other one)
+                            // WE: lgkmcnt(0) HERE, where the only LDS operations in flight are the next group's reads from the top of the step
+                            // (the previous step's stores and adds have retired in front of them).  The next step then opens without a wait;
+                            // left to the compiler, its wait for the record at the top also covers the ring stores / histogram adds below,
+                            // which nothing reads before a drain -- and a drain queues its reads behind them in the same wave's LDS queue.
+                            // (the sched_barrier keeps it here: nothing ties the wait to the classifier, and the scheduler lifts it to the end of
+                            //  the chi2, which leaves the reads half the time to arrive)
+                            if constexpr (WE) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xc07f); }
                             // -> the object's buffer (ballot + mbcnt compaction); its fill level is a wave-uniform scalar
                             const unsigned long long mask = __ballot(c);
                             // (v_mbcnt adds its count to a base: the fill level)  < 64 wait when a group begins, a group adds at most 64: never past CAP
@@ -929,13 +953,23 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
 #if defined(FZ_DIAG_NODRAIN)
                             if (hs.pend[o] >= DTHR) { hs.pend[o] -= 64; }
 #else
-                    if constexpr (SLOW) { const int lim = flush ? 1 : DTHR; while (hs.pend[o] >= lim) drain(o, std::true_type{}); }     // (flush: a change of pattern follows)
-                    else { while (hs.pend[o] >= DTHR) drain(o, std::false_type{}); }
+                    if constexpr (SLOW) { const int lim = flush ? 1 : DTHR; while (hs.pend[o] >= lim) drain(o, std::true_type{}, lane); }     // (flush: a change of pattern follows)
+                    else { while (hs.pend[o] >= DTHR) drain(o, std::false_type{}, lane); }
 #endif
                         }
                     }
                 }
         };
+        // the tile's wait for the staged copy + barrier (every wave meets it exactly once per tile)
+        auto tile_barrier = [&]() {
+#if !defined(FZ_DIAG_NOBARRIER)
+            __syncthreads();
+#endif
+        };
+        // SEAM: the first group's record and label words of the tile about to run, read by the tile in front of it (by the round's prologue
+        // for tile 0): the registers the step keeps live across its body anyway, now also across the tile loop's back edge
+        [[maybe_unused]] typename SRC::MR mseam[MP];
+        [[maybe_unused]] int tagseam[MP];
         // slowc (SEG): the tile goes group by group through the code that can change the pattern; else it is taken to be "pure" (below)
         auto run_tile = [&](const double* cur, double* nxt, int t, auto tailc, auto slowc) {
             constexpr bool TAIL = decltype(tailc)::value;
@@ -953,7 +987,10 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                 if constexpr (pure) {
                     typename SRC::MR mn[PF ? MP : 1];
                     int tagn[MP];
-                    if constexpr (PF) {
+                    if constexpr (SEAM) {
+#pragma unroll
+                        for (int q = 0; q < MP; ++q) { mn[q] = mseam[q]; tagn[q] = tagseam[q]; }
+                    } else if constexpr (PF) {
 #pragma unroll
                         for (int q = 0; q < MP; ++q) {
                             src.template load_model_lds<TILE>(cur, q * 64 + lane, mn[q]);
@@ -976,6 +1013,24 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                             for (int q = 0; q < MP; ++q) {
                                 src.template load_model_lds<TILE>(cur, (st + MP + q) * 64 + lane, mn[q]);
                                 tagn[q] = tags[(st + MP + q) * 64 + lane];
+                            }
+                        }
+                        if constexpr (SEAM) {
+                            if (st + MP >= TILE / 64) {
+                                // the tile's LAST trip: the barrier stands HERE, not behind it.  Every wave has its reads of `cur` behind it
+                                // (this trip's record arrived a step ago) and its share of `nxt` staged five steps ago, so nobody waits long;
+                                // behind the barrier `nxt` is whole and nobody reads `cur` again -- tile t + 2 may be staged into it as before.
+                                // The trip's prefetch slot, empty otherwise, takes the NEXT tile's first group.  (The last tile, the tail
+                                // form, has no successor.)
+                                tile_barrier();
+                                if constexpr (!TAIL) {
+                                    const int32_t* tagx = reinterpret_cast<const int32_t*>(nxt + TDR);
+#pragma unroll
+                                    for (int q = 0; q < MP; ++q) {
+                                        src.template load_model_lds<TILE>(nxt, q * 64 + lane, mseam[q]);
+                                        tagseam[q] = tagx[q * 64 + lane];
+                                    }
+                                }
                             }
                         }
                         // AHD: the reads above stay in front of the chi2 (left to itself the scheduler sinks them below it, and the next step
@@ -1016,10 +1071,19 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                     if (++hs.tick == hs.next) { hs.next = hs.tick < 3 ? hs.tick + 1 : hs.tick + 5; refresh_bars(); }
                 }
             }
-#if !defined(FZ_DIAG_NOBARRIER)
-            __syncthreads();
-#endif
+            if constexpr (SEAM && pure) { if (!work) tile_barrier(); }      // (a wave without work has staged its share: the tile's one barrier)
+            else tile_barrier();
         };
+        if constexpr (SEAM) {
+            if (work) {
+                const int32_t* tag0 = reinterpret_cast<const int32_t*>(tileA + TDR);
+#pragma unroll
+                for (int q = 0; q < MP; ++q) {
+                    src.template load_model_lds<TILE>(tileA, q * 64 + lane, mseam[q]);
+                    tagseam[q] = tag0[q * 64 + lane];
+                }
+            }
+        }
         if constexpr (!SEG) {
             for (int t = 0; t < ntiles; t += 2) {
                 if (t + 1 < ntiles) run_tile(tileA, tileB, t, std::false_type{}, std::false_type{}); else run_tile(tileA, tileB, t, std::true_type{}, std::false_type{});
@@ -1075,8 +1139,12 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                 if constexpr (!KRT && LEAN) lrf = uniform_d(lnl_fin(K));
                 double* row = rows + o * acc_stride;
                 double wbest_run = 0.0;
+                // (SEAM: likewise the lane's index for the last drains and the write of the output row: the ring address and the 64-bit row
+                //  offset derived from it are formed here, per object, and not held from the kernel's entry)
+                int lanef = lane;
+                if constexpr (SEAM) asm volatile("" : "+v"(lanef));
                 if constexpr (!EXACT) {
-                    while (hs.pend[o] > 0) drain(o, std::integral_constant<bool, SEG>{});
+                    while (hs.pend[o] > 0) drain(o, std::integral_constant<bool, SEG>{}, lanef);
                 } else {
                     wbest_run = wave_max(hs.Sc[o]);
                 }
@@ -1152,7 +1220,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                         continue;
                     }
                 }
-                kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lane, ok ? 1.0 / stot : 1.0, true);
+                kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true);
             }
         }
         __syncthreads();
