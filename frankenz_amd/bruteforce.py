@@ -502,6 +502,85 @@ class BruteForce():
             raise ValueError("Fits have not been computed.")
         return model_weight_sampler(self.fit_lnlike, device=self._device)
 
+    def fit_sparse(self, data, data_err, data_mask, Nkeep=256, wt_thresh=1e-3, lprob_func=None, lprob_args=None, lprob_kwargs=None,
+                   track_scale=False, resident=False, verbose=True):
+        """Extension (no reference counterpart; docs/sparse_fits.md): one exhaustive fit that leaves, per object, the exact ``Nkeep``
+        models of largest ln-posterior among those with ``wt > wt_thresh * max(wt)`` (``wt_thresh`` 0 or None: no cut), in the
+        layout ``NearestNeighbors.fit`` leaves -- a ``SparseFits`` whose ``predict`` / ``sample`` / ``weight_sampler`` are the k-NN
+        consumers.  Column 0 is the MAP model; ties go to the smaller model index.  ``lmap`` / ``levid`` are those of the full rows
+        and ``cover()`` the share of the posterior the sparse rows hold.  No attribute of this object is touched.
+
+        ``lprob_func`` as in ``fit_sample``; a foreign callable runs per object on the host and its ln-posterior rows are
+        sparsified ``_HOST_CHUNK`` objects at a time.  ``resident=True`` leaves ``neighbors``, ``Nneighbors``, ``fit_lnlike`` and
+        ``fit_lnprob`` as device arrays of the engine (nothing of size N x Nkeep crosses PCIe; the other ``fit_*`` are then None);
+        device arrays for ``data`` as in ``fit_sample`` (built-in likelihood only)."""
+        from .sparse import SparseFits, check_keep
+        prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
+        W, lncut = check_keep(Nkeep, wt_thresh, self.NMODEL)
+        on_dev = hasattr(data, "data_ptr")
+        if host is not None and (resident or on_dev):
+            raise NotImplementedError("device arrays / `resident=True` need the built-in likelihood")
+        Ndata = int(data.shape[0]) if on_dev else len(data)
+        lmap, levid, lnkept = np.zeros(Ndata), np.zeros(Ndata), np.zeros(Ndata)
+        if host is not None:
+            eng = get_engine(self._device)
+            nbr = np.full((Ndata, W), -99, dtype=np.int64)
+            cnt = np.zeros(Ndata, dtype=np.int64)
+            pads = (-np.inf, -np.inf, -np.inf, 0, np.inf, 1., 0.)
+            nout = 7 if track_scale else 5
+            fits = [np.full((Ndata, W), pads[k], dtype=np.int64 if k == 3 else np.float64) for k in range(nout)]
+            for lo in range(0, Ndata, _HOST_CHUNK):
+                hi = min(Ndata, lo + _HOST_CHUNK)
+                res = []
+                plane = np.empty((hi - lo, self.NMODEL))
+                for i in range(lo, hi):
+                    res.append(host(data[i], data_err[i], data_mask[i], self))
+                    plane[i - lo] = res[-1][2]
+                    _progress(verbose, 'Fitting object', i + 1, Ndata)
+                eng.sparsify_logwt(plane, W, lncut, nbr[lo:hi], cnt[lo:hi], lmap=lmap[lo:hi], levid=levid[lo:hi], lnkept=lnkept[lo:hi],
+                                   n=hi - lo, M=self.NMODEL)
+                for i in range(lo, hi):
+                    sel = nbr[i, :cnt[i]]
+                    for k in range(nout):
+                        fits[k][i, :cnt[i]] = np.asarray(res[i - lo][k])[sel]
+            fits += [None] * (7 - nout)
+            out = SparseFits(nbr, cnt, self.NMODEL, lmap, levid, lnkept, fits[0], fits[1], fits[2], fits[3], fits[4], fits[5], fits[6],
+                             device=self._device)
+        else:
+            opts = like_opts(lprob_kwargs)
+            eng = self._engine()
+            if on_dev:
+                _device_objects(data, data_err, data_mask)
+                x, xe, xm, obj = data, data_err, data_mask, None
+            else:
+                obj = HostObjects(data, data_err, data_mask)
+                x, xe, xm = obj.x, obj.xe, obj.xm
+            free = track_scale and bool(opts.free_scale)
+            if resident:
+                new = lambda dt: eng.device_empty((Ndata, W), dt)
+                nbr, cnt = new(np.int64), eng.device_empty((Ndata,), np.int64)
+                lnl, lpb = new(np.float64), new(np.float64)
+                lpr = chi2 = ndim = sc = se = None
+            else:
+                new = lambda dt: np.empty((Ndata, W), dtype=dt)
+                nbr, cnt = new(np.int64), np.zeros(Ndata, dtype=np.int64)
+                lpr, lnl, lpb, chi2, ndim = new(np.float64), new(np.float64), new(np.float64), new(np.float64), new(np.int64)
+                sc, se = (new(np.float64), new(np.float64)) if free else (None, None)
+            if Ndata:
+                eng.fit_sparse(x, xe, xm, opts, prior.chunk(0, Ndata, Ndata) if prior is not None else None, W, lncut, nbr, cnt,
+                               lnprior=lpr, lnlike=lnl, lnprob=lpb, chi2=chi2, ndim=ndim, scale=sc, scale_err=se, lmap=lmap, levid=levid,
+                               lnkept=lnkept, n=Ndata)
+            if obj is not None:
+                obj.writeback()
+            if not resident and not free and track_scale:       # (a fixed scale: 1 and 0 throughout, as ``fit`` leaves them)
+                sc, se = np.ones((Ndata, W)), np.zeros((Ndata, W))
+            _progress(verbose, 'Fitting object', Ndata, Ndata)
+            out = SparseFits(nbr, cnt, self.NMODEL, lmap, levid, lnkept, lpr, lnl, lpb, ndim, chi2, sc, se, device=self._device)
+        if verbose:
+            sys.stderr.write('\n')
+            sys.stderr.flush()
+        return out
+
     def fit_predict(self, data, data_err, data_mask, model_labels, model_label_errs,
                     lprob_func=None, label_dict=None, label_grid=None, kde_args=None,
                     kde_kwargs=None, lprob_args=None, lprob_kwargs=None, return_gof=False,

@@ -20,6 +20,7 @@
 #include "fz_synphot.h"
 #include "fz_draw.h"
 #include "fz_mw.h"
+#include "fz_sparse.h"
 
 using namespace fz;
 
@@ -1239,6 +1240,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_diag_host.inc"
 #include "fz_synphot_host.inc"
 #include "fz_draw_host.inc"
+#include "fz_sparse_host.inc"
 #include "fz_mw_host.inc"
 
 #ifdef FZ_KM_STATS

@@ -141,6 +141,8 @@ struct fz_ctx {
     DevBuf d_draw[6];
     // model-weight sampler (fz_mw_host.inc): the error flags of a call; the block partials of sum(g) and their sum
     DevBuf d_mw[2];
+    // sparse fits (fz_sparse_host.inc): lnkept, the kept ln-prob rows, the gathered rows of one plane at a time
+    DevBuf d_sparse[3];
 
     std::vector<DevBuf*> all_bufs() {
         std::vector<DevBuf*> v = {&d_y, &d_ye2, &d_ye, &d_rec0, &d_rec1, &d_ye2c, &d_mbits, &d_lgA, &d_lgB, &d_widths, &d_offsets, &d_kern, &d_pos,
@@ -152,6 +154,7 @@ struct fz_ctx {
         for (auto& b : d_mc) v.push_back(&b);
         for (auto& b : d_draw) v.push_back(&b);
         for (auto& b : d_mw) v.push_back(&b);
+        for (auto& b : d_sparse) v.push_back(&b);
         return v;
     }
 };

@@ -339,6 +339,23 @@ class Engine(object):
                                               float(distance_upper_bound), C.byref(opts), self._prior_lerp_struct(prior), up, k0, k1,
                                               int(first), int(S), ptr(neighbors), ptr(nnbr), ptr(idx), ptr(lmap), ptr(levid)))
 
+    # -- sparse rows out of an exhaustive fit (docs/sparse_fits.md; fz_sparse.h) ----
+    def sparsify_logwt(self, logwt, W, lncut, neighbors, nnbr, vals=None, lmap=None, levid=None, lnkept=None, n=None, M=None):
+        """fz_sparsify_logwt: per row of ``logwt`` (n, M) the ``W`` largest entries within ``lncut`` of its max -> ``neighbors``
+        (n, W) int64, ``nnbr`` (n) int64 [, ``vals`` (n, W), ``lmap`` / ``levid`` of the full row, ``lnkept``]"""
+        n = len(logwt) if n is None else n
+        M = logwt.shape[1] if M is None else M
+        check(self.lib.fz_sparsify_logwt(self.h, ptr(logwt), int(n), int(M), int(W), float(lncut), ptr(neighbors), ptr(nnbr), ptr(vals),
+                                         ptr(lmap), ptr(levid), ptr(lnkept)))
+
+    def fit_sparse(self, x, xe, xm, opts, prior, W, lncut, neighbors, nnbr, lnprior=None, lnlike=None, lnprob=None, chi2=None, ndim=None,
+                   scale=None, scale_err=None, lmap=None, levid=None, lnkept=None, n=None):
+        """fz_fit_sparse: objects -> the ``W`` best models each of the uploaded set, in the k-NN layout; ``prior`` as in ``fit_prior``"""
+        n = len(x) if n is None else n
+        check(self.lib.fz_fit_sparse(self.h, ptr(x), ptr(xe), ptr(xm), int(n), C.byref(opts), self._prior_lerp_struct(prior), int(W),
+                                     float(lncut), ptr(neighbors), ptr(nnbr), ptr(lnprior), ptr(lnlike), ptr(lnprob), ptr(chi2), ptr(ndim),
+                                     ptr(scale), ptr(scale_err), ptr(lmap), ptr(levid), ptr(lnkept)))
+
     # -- Gibbs over model weights (docs/model_weights.md; fz_mw.h) ----------------
     def mw_sweep(self, rows, n, W, M, lnw, counts, u=None, key=None, first=0, sweep=0, neighbors=None, nnbr=None, assign=None):
         """fz_mw_sweep: one draw per row of ``rows + lnw[neighbors]`` -> ``counts`` (M) int64 [and ``assign`` (n) int64]"""

@@ -17,7 +17,7 @@ import numpy as np
 from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
-           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels"]
+           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt"]
 
 
 def _ndim_dtype(data_mask, models_mask):
@@ -218,6 +218,26 @@ def sample_labels(idx, model_labels, model_label_errs=None, rstate=None):
         out = rstate.normal(out, np.asarray(model_label_errs, dtype=np.float64)[safe])
     out[bad] = np.nan
     return out
+
+
+def sparsify_logwt(logwt, Nkeep=256, wt_thresh=1e-3, device=None):
+    """Sparse rows out of stored or foreign dense rows of ln-weights (extension; docs/sparse_fits.md): per row of ``logwt``
+    ``(Ndata, Nmodel)`` (NumPy or a device array) the exact ``Nkeep`` largest entries among those with ``wt > wt_thresh * max(wt)``,
+    as a ``sparse.SparseFits`` in which only ``fit_lnprob`` is set (NumPy arrays)."""
+    from .sparse import SparseFits, check_keep
+    lw = logwt if hasattr(logwt, "data_ptr") else np.ascontiguousarray(logwt, dtype=np.float64)
+    if len(lw.shape) != 2 or (hasattr(lw, "data_ptr") and not (lw.element_size() == 8 and lw.is_contiguous())):
+        raise ValueError("`logwt` must be a C-contiguous float64 (Ndata, Nmodel) array; got shape %s" % (tuple(lw.shape),))
+    N, M = (int(v) for v in lw.shape)
+    if M < 1:
+        raise ValueError("`logwt` has rows without entries")
+    W, lncut = check_keep(Nkeep, wt_thresh, M)
+    nbr, cnt = np.full((N, W), -99, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    vals = np.full((N, W), -np.inf)
+    lmap, levid, lnkept = np.zeros(N), np.zeros(N), np.zeros(N)
+    if N:
+        get_engine(device).sparsify_logwt(lw, W, lncut, nbr, cnt, vals=vals, lmap=lmap, levid=levid, lnkept=lnkept, n=N, M=M)
+    return SparseFits(nbr, cnt, M, lmap, levid, lnkept, fit_lnprob=vals, device=device)
 
 
 def gaussian(mu, std, x):

@@ -540,6 +540,28 @@ int  fz_mw_chain(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const in
                  const double* alpha, double* lnw, uint32_t key0, uint32_t key1, int64_t first, uint64_t sweep0, int32_t nsweeps,
                  int64_t* counts, double* pos, int64_t* counts_all);
 
+/* ---- sparse rows out of an exhaustive fit (extension, no reference counterpart; docs/sparse_fits.md) ----
+ * For a row r[0..L) of ln-weights, a cap W >= 1 and a cut lncut < 0 (-inf allowed): a nan among the entries, or a max that is not
+ * finite, keeps nothing (Nneighbors = 0).  Else m = max r, entry j is eligible iff r_j - m > lncut (one IEEE subtraction, strict), and
+ * kept are the first min(W, E) eligible entries in the order (value descending, index ascending; compared as doubles), stored in that
+ * order: column 0 is the MAP model, and the result for W' < W is the first W' columns of the result for W.  Layout of the k-NN
+ * fitter: neighbors (N, W) int64 padded with -99, nnbr (N) int64, rows (N, W) padded like NearestNeighbors' (lnprior, lnlike, lnprob
+ * -inf; chi2 +inf; Ndim 0; scale 1; scale_err 0).  lmap / levid: of the FULL row, bit for bit those of fz_draw_logwt; lnkept: the
+ * logsumexp of the kept entries (-inf when nothing is kept).  The result is a function of (row, W, lncut) alone.
+ * Refusals, before any launch: W > 4096 (FZ_SPARSE_WMAX) or rows longer than 2^20 (FZ_DRAW_LMAX): -5; W < 1, lncut >= 0 or nan: -4.
+ *
+ * fz_sparsify_logwt -- extension, no reference counterpart.  logwt (N, M) rows, host or device, staged in chunks from the workspace
+ *   limit; neighbors (N, W), nnbr (N) required; vals (N, W), lmap, levid, lnkept (N) or NULL.
+ * fz_fit_sparse -- extension, no reference counterpart.  Objects -> sparse rows with the built-in likelihood (every mode) and an
+ *   optional ln-prior (as fz_fit_draw): per chunk the planes of fz_fit that are asked for, the selection on the ln-prob plane and a
+ *   gather per other plane; chunks sized from the workspace limit by the number of planes formed.  Every per-pair output may be NULL;
+ *   a kept entry of one is the plane's value at (i, neighbors[i][t]), bit for bit.  x, xe, xm are cleaned in place like fz_fit. */
+int  fz_sparsify_logwt(fz_ctx* ctx, const double* logwt, int64_t N, int64_t M, int64_t W, double lncut, int64_t* neighbors, int64_t* nnbr,
+                       double* vals, double* lmap, double* levid, double* lnkept);
+int  fz_fit_sparse(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* opts, const fz_prior_lerp* prior, int64_t W,
+                   double lncut, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
+                   int64_t* ndim, double* scale, double* scale_err, double* lmap, double* levid, double* lnkept);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
