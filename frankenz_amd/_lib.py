@@ -43,6 +43,12 @@ class PriorLerp(C.Structure):
     _fields_ = [("table", C.c_void_p), ("P", C.c_int64), ("rows", C.c_void_p), ("frac", C.c_void_p)]
 
 
+class KnnMap(C.Structure):
+    """fz_knn_map: the k-NN feature map of the device's Monte-Carlo draws, one fp64 constant per band"""
+    _fields_ = [("kind", C.c_int32), ("reserved_", C.c_int32),
+                ("skynoise", C.c_double * 32), ("zeropoints", C.c_double * 32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_planes", C.c_double), ("n_planes", C.c_int64),
                 ("ms_fused", C.c_double), ("n_fused", C.c_int64),
@@ -139,6 +145,8 @@ ABI = {
     "fz_mw_chain": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, C.c_uint32, C.c_uint32, _I64, C.c_uint64, _I32, _P, _P, _P]),
     "fz_sparsify_logwt": (C.c_int, [_P, _P, _I64, _I64, _I64, _F64] + [_P] * 6),
     "fz_fit_sparse": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _I64, _F64] + [_P] * 12),
+    "fz_knn_draw_features": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(KnnMap), C.c_uint32, C.c_uint32, _I64, _P]),
+    "fz_knn_draw_trees": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, C.POINTER(KnnMap), C.c_uint32, C.c_uint32, _P]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 #include "fz_cdf.h"
 #include "fz_knn.h"
 #include "fz_knn_mfma.h"
+#include "fz_knn_mc.h"
 #include "fz_launch.h"
 #include "fz_modec.h"
 #include "fz_summary.h"
@@ -1231,6 +1232,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 }
 
 #include "fz_knn_host.inc"
+#include "fz_knn_mc_host.inc"
 #include "fz_summary_host.inc"
 #include "fz_net_host.inc"
 #include "fz_train_host.inc"

@@ -8,15 +8,17 @@ __global__ void k_knn_pack(const float* in, int K, int64_t M, int F, int FT, int
         out[((size_t)t * FT + f) * Mp + j] = (j < M && f < F) ? in[((size_t)t * M + j) * F + f] : 0.0f;
 }
 
-extern "C" int fz_knn_upload_trees(fz_ctx* c, const float* feats, int32_t K, int64_t M, int32_t F) {
-    if (!c || !feats) return fail(-1, "fz_knn_upload_trees: NULL argument");
-    if (K <= 0 || M <= 0 || F <= 0) return fail(-1, "fz_knn_upload_trees: bad shape");
-    if (!c->M || M != c->M || F != c->B) return fail(-1, "fz_knn_upload_trees: feature sets (%lld,%d) must match the uploaded models (%lld,%d)",
+// the shape checks of a set of feature sets against the uploaded models
+static int knn_trees_shape(const fz_ctx* c, const char* who, int32_t K, int64_t M, int32_t F) {
+    if (K <= 0 || M <= 0 || F <= 0) return fail(-1, "%s: bad shape", who);
+    if (!c->M || M != c->M || F != c->B) return fail(-1, "%s: feature sets (%lld,%d) must match the uploaded models (%lld,%d)", who,
                                                    (long long)M, F, (long long)c->M, c->B);
-    HIPCHK(hipSetDevice(c->device));
+    return 0;
+}
+// The shared tail of fz_knn_upload_trees and fz_knn_draw_trees: the raw (K,M,F) float32 block sits in d_pl[0] (copied in, or drawn by
+// k_knn_mc_sets) and becomes the resident sets -- the SoA copy, the k-d ordering, the operands of the matrix-pipe search.
+static int knn_install_trees(fz_ctx* c, int32_t K, int64_t M, int32_t F) {
     const size_t raw = (size_t)K * M * F * 4;
-    FZCHK(c->d_pl[0].ensure(raw));
-    FZCHK(copy_in(c, c->d_pl[0].p, feats, raw));
     FZCHK(c->d_trees.ensure((size_t)K * c->BT * c->Mp * 4));
     {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
@@ -100,6 +102,16 @@ extern "C" int fz_knn_upload_trees(fz_ctx* c, const float* feats, int32_t K, int
     }
     c->knn_K = K; c->knn_F = F; c->knn_M = M;
     return 0;
+}
+
+extern "C" int fz_knn_upload_trees(fz_ctx* c, const float* feats, int32_t K, int64_t M, int32_t F) {
+    if (!c || !feats) return fail(-1, "fz_knn_upload_trees: NULL argument");
+    FZCHK(knn_trees_shape(c, "fz_knn_upload_trees", K, M, F));
+    HIPCHK(hipSetDevice(c->device));
+    const size_t raw = (size_t)K * M * F * 4;
+    FZCHK(c->d_pl[0].ensure(raw));
+    FZCHK(copy_in(c, c->d_pl[0].p, feats, raw));
+    return knn_install_trees(c, K, M, F);
 }
 
 #ifdef FZ_KM_STATS

@@ -387,6 +387,24 @@ class Engine(object):
         check(self.lib.fz_knn_upload_trees(self.h, ptr(f), K, M, F))
         self._trees_key = key
 
+    def knn_draw_features(self, x, xe, n, F, fmap, key, first, q):
+        """fz_knn_draw_features: ``q = map(x + xe z)`` (n, F) float64 for objects ``first .. first + n - 1`` under the Philox ``key``;
+        ``x``, ``xe``, ``q`` host or device, the rows as given (not cleaned); ``fmap``: a ``_lib.KnnMap``"""
+        check(self.lib.fz_knn_draw_features(self.h, ptr(x), ptr(xe), int(n), int(F), C.byref(fmap), int(key[0]) & 0xFFFFFFFF,
+                                            int(key[1]) & 0xFFFFFFFF, int(first), ptr(q)))
+
+    def knn_draw_trees(self, models, models_err, K, fmap, key, feats_out):
+        """fz_knn_draw_trees: the K feature sets drawn on the device from the user's ``models`` / ``models_err`` (the shape of the
+        uploaded model set) and installed as the resident sets; ``feats_out`` (K, M, F) float32 receives them and their content key
+        becomes the engine's, so that ``knn_upload_trees`` of the same floats sends nothing.  Returns that key."""
+        y, ye = _f64(models), _f64(models_err)
+        M, F = y.shape
+        self._trees_key = None
+        check(self.lib.fz_knn_draw_trees(self.h, ptr(y), ptr(ye), int(K), int(M), int(F), C.byref(fmap), int(key[0]) & 0xFFFFFFFF,
+                                         int(key[1]) & 0xFFFFFFFF, ptr(feats_out)))
+        self._trees_key = _digest(feats_out)
+        return self._trees_key
+
     def knn_query(self, q, k, distance_upper_bound, idx, n=None, lp_norm=2):
         n = len(q) if n is None else n
         check(self.lib.fz_knn_query(self.h, ptr(q), n, int(k), float(lp_norm), float(distance_upper_bound), ptr(idx)))

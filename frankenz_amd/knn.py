@@ -8,9 +8,11 @@ first-appearance union (<= K*k models) -> the usual likelihood / weights / KDE o
 subset.  Here the K tree queries are replaced by an EXACT brute-force top-k search
 on the GPU (an exact answer satisfies KDTree.query's (1+eps) guarantee; it can differ
 from SciPy's pick only among near-ties within eps), and the subset likelihood + PDF
-stack is one wave per object.  The random draws stay on the host with the caller's
-``numpy.random.RandomState`` so the stream -- and therefore the result -- is the
-reference's.
+stack is one wave per object.  By default the random draws stay on the host with the
+caller's ``numpy.random.RandomState`` so the stream -- and therefore the result -- is the
+reference's; ``feature_draws='device'`` / ``query_draws='device'`` (extensions, docs/knn.md)
+draw the feature sets / the query features on the GPU from a Philox key taken from that
+``RandomState``: the reference's law, not its realisation.
 """
 import copy
 import sys
@@ -24,6 +26,74 @@ from .engine import HostObjects, _digest, get_engine, kde_opts, like_opts, merge
 __all__ = ["NearestNeighbors"]
 
 _GEN_CHUNK = 4096
+
+_KNN_KEY_XOR = 0x6B6E6D63     # second key word of the Monte-Carlo draws on the device (csrc/fz_philox.h: FZ_KNN_KEY_XOR)
+_FMAP_KINDS = {'identity': 0, 'magnitude': 1, 'luptitude': 2}
+_FMAP_NAMES = {'identity': (), 'magnitude': ('zeropoints',), 'luptitude': ('skynoise', 'zeropoints')}     # the maps' own signatures
+
+
+def _philox_normal(key, first, n, F, set):
+    """The standard normals the device draws for rows ``first .. first + n - 1`` and bands ``0 .. F - 1`` (``(n, F)`` float64; the
+    NumPy twin of csrc/fz_philox.h: philox_normal2).  Philox4x32-10 under the key ``(key[0], key[1] ^ 0x6B6E6D63)`` at the counter
+    ``(row lo, row hi, band >> 1, set)``; Box-Muller of ``u1 = 1 - U(words 0, 1)`` in (0, 1] and ``u2 = U(words 2, 3)`` in [0, 1):
+    ``r = sqrt(-2 ln u1)``, an even band takes ``r cos(2 pi u2)``, an odd one ``r sin(2 pi u2)``.  ``set``: 0 for the query draws of
+    objects, ``1 + t`` for feature set ``t`` of the models."""
+    from .samplers import _philox4x32
+    n, F, npair = int(n), int(F), (int(F) + 1) // 2
+    rows = np.repeat(np.arange(n, dtype=np.uint64) + np.uint64(first), npair)
+    pair = np.tile(np.arange(npair, dtype=np.uint64), n)
+    ctr = np.stack([rows & np.uint64(0xFFFFFFFF), rows >> np.uint64(32), pair, np.full(n * npair, int(set), dtype=np.uint64)], axis=1)
+    o = _philox4x32((int(key[0]) & 0xFFFFFFFF, (int(key[1]) & 0xFFFFFFFF) ^ _KNN_KEY_XOR), ctr)
+
+    def u53(a, b):
+        return ((a >> np.uint32(5)) * 67108864.0 + (b >> np.uint32(6))) / 9007199254740992.0
+
+    u1, u2 = 1. - u53(o[:, 0], o[:, 1]), u53(o[:, 2], o[:, 3])
+    r, a = np.sqrt(-2. * np.log(u1)), 6.283185307179586 * u2
+    z = np.stack([r * np.cos(a), r * np.sin(a)], axis=1).reshape(n, 2 * npair)
+    return np.ascontiguousarray(z[:, :F])
+
+
+def _fmap_bands(kind, fmap_args, fmap_kwargs, F):
+    """-> ``(skynoise, zeropoints)``, one float64 per band, as ``pdf.magnitude`` / ``pdf.luptitude`` would bind ``fmap_args`` /
+    ``fmap_kwargs`` (positional arguments in the order of the map's own signature, surplus ones ignored like ``*args``; scalars
+    broadcast)."""
+    names = _FMAP_NAMES[kind]
+    vals = dict(zip(names, fmap_args))
+    for nm in names:
+        if nm in fmap_kwargs:
+            if nm in vals:
+                raise TypeError("%s() got multiple values for argument '%s'" % (kind, nm))
+            vals[nm] = fmap_kwargs[nm]
+    out = []
+    for nm in ('skynoise', 'zeropoints'):
+        v = np.asarray(vals.get(nm, 1.), dtype=np.float64)
+        try:
+            out.append(np.ascontiguousarray(np.broadcast_to(v, (F,))))
+        except ValueError:
+            raise ValueError("`%s` must be a scalar or one value per band (%d) for draws on the device; got shape %s" % (nm, F, v.shape))
+    return out[0], out[1]
+
+
+def _fmap_struct(kind, fmap_args, fmap_kwargs, F):
+    """the ``fz_knn_map`` of a feature map by name"""
+    from ._lib import KnnMap
+    if F > 32:
+        raise NotImplementedError("at most 32 bands (got %d)" % F)
+    sky, zp = _fmap_bands(kind, fmap_args, fmap_kwargs, F)
+    m = KnnMap()
+    m.kind = _FMAP_KINDS[kind]
+    for b in range(32):
+        m.skynoise[b] = sky[b] if b < F else 1.
+        m.zeropoints[b] = zp[b] if b < F else 1.
+    return m
+
+
+def _check_draws(name, value, query_features=None):
+    if value not in ('host', 'device'):
+        raise ValueError("`%s` must be 'host' or 'device' (got %r)" % (name, value))
+    if value == 'device' and query_features is not None:
+        raise ValueError("`query_features` and `%s='device'` exclude each other: the features are given or drawn" % name)
 
 
 class _FeatureSet(object):
@@ -64,16 +134,20 @@ class _PreparedKnn(object):
         eng.set_labels(*self._labels)
         self._keys = (eng._models_key, eng._dict_key, eng._labels_key, eng._trees_key)
 
-    def run(self, data, data_err, data_mask, out=None, query_features=None, rstate=None):
+    def run(self, data, data_err, data_mask, out=None, query_features=None, rstate=None, query_draws='host'):
         """-> (pdfs, lmap, levid).  ``data*``: NumPy arrays or contiguous float64 tensors on the engine's GPU (cleaned in place
         by the library, pdf.py:310-311); ``query_features``: (Ndata, Nfilt) float64, NumPy or device tensor -- when None they are
         drawn here from ``rstate`` exactly as knn.py:830-832 does (on the host: the stream is NumPy's), which needs the objects
-        on the host (device tensors are copied back for that one step)."""
+        on the host (device tensors are copied back for that one step) -- or, with ``query_draws='device'``, on the GPU under a
+        Philox key taken from ``rstate`` (``nn.query_key``): device tensors then stay where they are."""
         nn, eng, Nx = self.nn, self.eng, self.Nx
+        _check_draws('query_draws', query_draws, query_features)
         self._ensure_resident()
         on_dev = hasattr(data, "data_ptr")
         Ndata = int(data.shape[0])
-        if query_features is None:
+        if query_draws == 'device':
+            query_features = nn._draw_query(data, data_err, rstate if rstate is not None else np.random, 'device')
+        elif query_features is None:
             hx, hxe = (data.cpu().numpy(), data_err.cpu().numpy()) if on_dev else (np.asarray(data), np.asarray(data_err))
             query_features = nn._query_features(hx, hxe, rstate if rstate is not None else np.random)
         q = query_features
@@ -123,7 +197,11 @@ class NearestNeighbors():
     realisations of the models (knn.py:33-38)."""
 
     def __init__(self, models, models_err, models_mask, leafsize=50, K=25, feature_map='luptitude',
-                 fmap_args=None, fmap_kwargs=None, rstate=None, verbose=True, device=None):
+                 fmap_args=None, fmap_kwargs=None, rstate=None, verbose=True, device=None, feature_draws='host'):
+        """knn.py:40-156.  Extension: ``feature_draws='device'`` draws the K feature sets on the GPU (docs/knn.md): ``rstate`` is
+        consumed by exactly one ``randint(0, 2**32, size=2, dtype=uint32)``, kept as ``feature_key``; the law of the sets is the
+        reference's, the realisation for a seed is not.  The default ``'host'`` is the reference's stream."""
+        _check_draws('feature_draws', feature_draws)
         self.models = models
         self.models_err = models_err
         self.models_mask = models_mask
@@ -153,6 +231,7 @@ class NearestNeighbors():
             fmap_kwargs = dict()
         self.fmap_args = fmap_args
         self.fmap_kwargs = fmap_kwargs
+        self._fmap_kind = feature_map if isinstance(feature_map, str) and feature_map in _FMAP_KINDS else None
         if feature_map == 'identity':
             def feature_map(x, xe, *args, **kwargs):
                 return x, xe
@@ -168,6 +247,16 @@ class NearestNeighbors():
         if rstate is None:
             rstate = np.random
         self.KDTrees = []
+        self.feature_key = None
+        self.query_key = None
+        if feature_draws == 'device':
+            self.feature_key = rstate.randint(0, 2**32, size=2, dtype=np.uint32)
+            self._draw_feature_sets(self.feature_key)
+            if verbose:
+                sys.stderr.write("\r{0}/{0} KDTrees constructed\n".format(self.K))
+                sys.stderr.flush()
+            self._uploaded = False
+            return
         for i, tree in enumerate(self._train_kdtrees(rstate=rstate)):
             if verbose:
                 sys.stderr.write("\r{0}/{1} KDTrees constructed".format(i + 1, self.K))
@@ -188,6 +277,17 @@ class NearestNeighbors():
             Y_t, Ye_t = np.array(self.feature_map(models_t, self.models_err, *self.fmap_args,
                                                   **self.fmap_kwargs), dtype='float32')
             yield _FeatureSet(Y_t, self.leafsize)
+
+    def _draw_feature_sets(self, key):
+        """the K feature sets of knn.py:158-188 drawn on the device (``fz_knn_draw_trees``): resident at once, and copied out as
+        ``KDTrees[t].data`` / ``_feats`` under the engine's content key -- a later ``_engine()`` sends nothing, and a re-upload after
+        another fitter has displaced the sets sends these very floats"""
+        eng = get_engine(self._device)
+        eng.upload_models(self.models, self.models_err, self.models_mask)
+        fmap = _fmap_struct(self._fmap_kind, self.fmap_args, self.fmap_kwargs, self.NDIM)
+        self._feats = np.empty((self.K, self.NMODEL, self.NDIM), dtype=np.float32)
+        self._feats_key = eng.knn_draw_trees(self.models, self.models_err, self.K, fmap, key, self._feats)
+        self.KDTrees = [_FeatureSet(self._feats[t], self.leafsize) for t in range(self.K)]
 
     # ------------------------------------------------------------------
     def _engine(self):
@@ -216,6 +316,58 @@ class NearestNeighbors():
         x_t = rstate.normal(data, data_err)
         y_t, _ = self.feature_map(x_t, data_err, *self.fmap_args, **self.fmap_kwargs)
         return np.ascontiguousarray(y_t, dtype=np.float64)
+
+    def _device_features(self, data, data_err, key, first=0):
+        """``fz_knn_draw_features``: the objects' Monte-Carlo features drawn on the GPU under the Philox ``key`` (rows as given:
+        before the library's in-place clean, as knn.py:830 draws); NumPy in -> NumPy out (a page-locked block), tensor in -> tensor"""
+        eng = get_engine(self._device)
+        fmap = _fmap_struct(self._fmap_kind, self.fmap_args, self.fmap_kwargs, self.NDIM)
+        if hasattr(data, "data_ptr"):
+            _device_objects(data, data_err, data_err)
+            if int(data.shape[1]) != self.NDIM:
+                raise ValueError("objects must have %d bands (got %d)" % (self.NDIM, int(data.shape[1])))
+            if hasattr(data, "is_cuda"):
+                import torch
+                q = torch.empty(tuple(data.shape), dtype=torch.float64, device=data.device)
+            else:
+                q = eng.device_empty(tuple(data.shape), np.dtype('float64'))
+            x, xe = data, data_err
+        else:
+            x, xe = np.ascontiguousarray(data, dtype=np.float64), np.ascontiguousarray(data_err, dtype=np.float64)
+            if x.ndim != 2 or x.shape != xe.shape or x.shape[1] != self.NDIM:
+                raise ValueError("objects and their errors must share a (Ndata, %d) shape" % self.NDIM)
+            q = pinned_empty(x.shape)
+        eng.knn_draw_features(x, xe, int(x.shape[0]), self.NDIM, fmap, key, first, q)
+        return q
+
+    def _draw_query(self, data, data_err, rstate, query_draws, first=0):
+        """the query features of a call, taken where knn.py:830-832 takes them: ``'host'`` from ``rstate.normal``; ``'device'`` one
+        Philox key from ``rstate`` (kept as ``query_key``) and the draw on the GPU"""
+        if rstate is None:
+            rstate = np.random
+        if query_draws == 'host':
+            return self._query_features(np.asarray(data), np.asarray(data_err), rstate)
+        self.query_key = rstate.randint(0, 2**32, size=2, dtype=np.uint32)
+        return self._device_features(data, data_err, self.query_key, first)
+
+    def query_features(self, data, data_err, rstate=None, draws='host', key=None, first=0):
+        """Extension: the objects' Monte-Carlo features of knn.py:830-832, ``(N, Nfilt)`` float64 -- what ``query_features=`` of the
+        fitting calls takes.  NumPy in -> NumPy out, tensor in -> tensor out.  ``draws='host'``: ``rstate.normal`` and the feature
+        map in NumPy, the reference's stream.  ``draws='device'``: drawn on the GPU under the two-word Philox ``key`` (None: one
+        ``rstate.randint(0, 2**32, size=2, dtype=uint32)``), row ``i`` at the counter of object ``first + i`` -- with
+        ``key=nn.query_key`` the features of the last call that drew its own (``knn._philox_normal`` gives the variates)."""
+        _check_draws('draws', draws)
+        if rstate is None:
+            rstate = np.random
+        if draws == 'device':
+            if key is None:
+                key = rstate.randint(0, 2**32, size=2, dtype=np.uint32)
+            return self._device_features(data, data_err, key, first)
+        if hasattr(data, "data_ptr"):
+            import torch
+            q = self._query_features(data.cpu().numpy(), data_err.cpu().numpy(), rstate)
+            return torch.from_numpy(q).to(data.device)
+        return self._query_features(np.asarray(data), np.asarray(data_err), rstate)
 
     def _alloc_fits(self, Ndata):
         """knn.py:812-821."""
@@ -257,7 +409,7 @@ class NearestNeighbors():
             valid = np.arange(W)[None, :] < self.Nneighbors[sl][:, None]
             self.fit_lnprior[sl] = np.where(valid, 0.0, -np.inf)          # knn.py:852: zeros on the subset
 
-    def _host_run(self, host, data, data_err, data_mask, rstate, track_scale, labels=None):
+    def _host_run(self, host, data, data_err, data_mask, rstate, track_scale, labels=None, query_draws='host'):
         """knn.py:355-388 / 826-874 with a user ``lprob_func``: the K searches run on the GPU, the
         first-appearance de-duplication (``pandas.unique``, knn.py:840) on the host,
         the callable is evaluated per object on its neighbour subset like the reference does, and -- with
@@ -266,7 +418,7 @@ class NearestNeighbors():
         if rstate is None:
             rstate = np.random
         eng = self._engine()
-        q = self._query_features(np.asarray(data), np.asarray(data_err), rstate)
+        q = self._draw_query(data, data_err, rstate, query_draws)
         Ndata = len(data)
         self.NDATA = Ndata
         self._alloc_fits(Ndata)
@@ -309,22 +461,23 @@ class NearestNeighbors():
 
     # ------------------------------------------------------------------
     def fit(self, data, data_err, data_mask, lprob_func=None, rstate=None, k=20, eps=1e-3, lp_norm=2,
-            distance_upper_bound=np.inf, lprob_args=None, lprob_kwargs=None, track_scale=False, verbose=True):
-        """knn.py:190-279."""
+            distance_upper_bound=np.inf, lprob_args=None, lprob_kwargs=None, track_scale=False, verbose=True, query_draws='host'):
+        """knn.py:190-279.  Extension: ``query_draws='device'`` draws the objects' features on the GPU (docs/knn.md)."""
+        _check_draws('query_draws', query_draws)
         prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
         opts = like_opts(lprob_kwargs) if host is None else None
         if rstate is None:
             rstate = np.random
         self._search_setup(k, eps, lp_norm, distance_upper_bound)
         if host is not None:
-            self._host_run(host, data, data_err, data_mask, rstate, track_scale)
+            self._host_run(host, data, data_err, data_mask, rstate, track_scale, query_draws=query_draws)
             _progress(verbose, 'Fitting object', len(data), len(data))
             if verbose:
                 sys.stderr.write('\n')
                 sys.stderr.flush()
             return
         eng = self._engine()
-        q = self._query_features(np.asarray(data), np.asarray(data_err), rstate)
+        q = self._draw_query(data, data_err, rstate, query_draws)
         obj = HostObjects(data, data_err, data_mask)
         Ndata = len(obj.x)
         self.NDATA = Ndata
@@ -337,9 +490,10 @@ class NearestNeighbors():
             sys.stderr.flush()
 
     def _fit(self, data, data_err, data_mask, lprob_func=None, rstate=None, lprob_args=None, lprob_kwargs=None,
-             track_scale=False, save_fits=True):
+             track_scale=False, save_fits=True, query_draws='host'):
         """Generator twin (knn.py:281-388): yields ``(idxs, Nidx, results)`` per object;
         uses the ``k / eps / lp_norm / dbound`` attributes like the reference."""
+        _check_draws('query_draws', query_draws)
         prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
         opts = like_opts(lprob_kwargs) if host is None else None
         if rstate is None:
@@ -347,11 +501,13 @@ class NearestNeighbors():
         self._search_setup(self.k, self.eps, self.lp_norm, self.dbound)
         if host is not None:
             keep = self if save_fits else copy.copy(self)
-            for r in keep._host_run(host, data, data_err, data_mask, rstate, track_scale):
+            for r in keep._host_run(host, data, data_err, data_mask, rstate, track_scale, query_draws=query_draws):
                 yield r
+            if keep is not self:
+                self.query_key = keep.query_key
             return
         eng = self._engine()
-        q = self._query_features(np.asarray(data), np.asarray(data_err), rstate)
+        q = self._draw_query(data, data_err, rstate, query_draws)
         obj = HostObjects(data, data_err, data_mask)
         Ndata = len(obj.x)
         self.NDATA = Ndata
@@ -370,12 +526,15 @@ class NearestNeighbors():
     # ------------------------------------------------------------------
     def fit_sample(self, data, data_err, data_mask, Nsamples, lprob_func=None, rstate=None, k=20, eps=1e-3, lp_norm=2,
                    distance_upper_bound=np.inf, lprob_args=None, lprob_kwargs=None, draws='device', return_gof=False,
-                   verbose=True, out=None, query_features=None):
+                   verbose=True, out=None, query_features=None, query_draws='host'):
         """Extension (twin of ``BruteForce.fit_sample``; docs/draws.md): ``Nsamples`` posterior draws per object over its
         neighbour subset; the values are MODEL indices (``-1`` throughout a row without a posterior).  Search arguments as in
         ``fit_predict``.  ``rstate`` is consumed by the query draw first (knn.py:830-832), as today; the Philox key
         (``draws='device'``, kept in ``philox_key``) or the uniforms (``draws='host'``) are drawn after it.  The ``fit_*`` arrays
-        are not filled (a user callable fills a scratch copy)."""
+        are not filled (a user callable fills a scratch copy).  ``query_draws='device'`` draws the query features on the GPU
+        under a key of their own (``query_key``), taken from ``rstate`` BEFORE the posterior key or uniforms: device objects then
+        need no ``query_features``."""
+        _check_draws('query_draws', query_draws, query_features)
         prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
         S = _check_nsamples(Nsamples)
         if rstate is None:
@@ -387,16 +546,20 @@ class NearestNeighbors():
             if out is not None or on_dev or query_features is not None:
                 raise NotImplementedError("device arrays / `out=` / `query_features` need the built-in likelihood")
             keep = copy.copy(self)
-            keep._host_run(host, data, data_err, data_mask, rstate, False)
+            keep._host_run(host, data, data_err, data_mask, rstate, False, query_draws=query_draws)
+            self.query_key = keep.query_key
             u, key = _draw_uniforms(rstate, draws, Ndata, S)
             self.philox_key = key
             res = keep._draw_stored(keep.fit_lnprob, S, u, key)
         else:
             opts = like_opts(lprob_kwargs)
             eng = self._engine()
-            if query_features is None:
+            if query_draws == 'device':
+                q = self._draw_query(data, data_err, rstate, 'device')
+            elif query_features is None:
                 if on_dev:
-                    raise NotImplementedError("device objects need `query_features` (the query draw is the host's)")
+                    raise NotImplementedError("device objects need `query_features` or query_draws='device' (the host's query "
+                                              "draw needs the objects on the host)")
                 q = self._query_features(np.asarray(data), np.asarray(data_err), rstate)
             else:
                 q = query_features if hasattr(query_features, "data_ptr") else np.ascontiguousarray(query_features, dtype=np.float64)
@@ -506,14 +669,17 @@ class NearestNeighbors():
                     rstate=None, k=20, eps=1e-3, lp_norm=2, distance_upper_bound=np.inf, label_dict=None,
                     label_grid=None, kde_args=None, kde_kwargs=None, lprob_args=None, lprob_kwargs=None,
                     return_gof=False, track_scale=False, verbose=True, save_fits=True, out=None,
-                    query_features=None):
+                    query_features=None, query_draws='host'):
         """knn.py:560-720.
 
         Extensions (no reference counterpart): ``out=(pdfs, lmap, levid)`` -- caller-allocated float64 arrays, NumPy or
         tensors on this engine's GPU -- receives the results in place; ``data`` / ``data_err`` / ``data_mask`` may be
         device tensors; ``query_features`` (Ndata, Nfilt) -- the objects' Monte-Carlo features of knn.py:830-832, NumPy or
         device tensor -- replaces the draw from ``rstate`` (a driver that shards the objects draws them once for all
-        ranks).  With device tensors throughout nothing crosses PCIe: query features, neighbour table and PDFs stay in HBM."""
+        ranks); ``query_draws='device'`` draws them on the GPU under a Philox key taken from ``rstate`` where the host draw is
+        taken (``query_key``; docs/knn.md).  With device tensors throughout nothing crosses PCIe: query features, neighbour table
+        and PDFs stay in HBM."""
+        _check_draws('query_draws', query_draws, query_features)
         prior, host = _check_lprob(lprob_func, lprob_args, self.NMODEL, lprob_kwargs)
         kde_kwargs = merge_kde_args(kde_args, kde_kwargs, label_dict is not None)
         if label_dict is None and label_grid is None:
@@ -529,12 +695,15 @@ class NearestNeighbors():
                 prep = self.prepare_fit_predict(model_labels, model_label_errs, label_dict=label_dict, label_grid=label_grid,
                                                 kde_kwargs=kde_kwargs, lprob_kwargs=lprob_kwargs, prior=prior, k=k, eps=eps,
                                                 lp_norm=lp_norm, distance_upper_bound=distance_upper_bound)
-                pdfs, lmap, levid = prep.run(data, data_err, data_mask, out=out, query_features=query_features, rstate=rstate)
+                pdfs, lmap, levid = prep.run(data, data_err, data_mask, out=out, query_features=query_features, rstate=rstate,
+                                             query_draws=query_draws)
                 return (pdfs, (lmap, levid)) if return_gof else pdfs
         if host is not None:
             keep = self if save_fits else copy.copy(self)
             pdfs, gof = keep._host_run(host, data, data_err, data_mask, rstate, track_scale,
-                                       labels=(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs))
+                                       labels=(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs),
+                                       query_draws=query_draws)
+            self.query_key = keep.query_key
             _progress(verbose, 'Generating PDF', len(data), len(data))
             if verbose:
                 sys.stderr.write('\n')
@@ -545,7 +714,7 @@ class NearestNeighbors():
         eng = self._engine()
         Nx = eng.set_labels(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs)
         q = (np.ascontiguousarray(query_features, dtype=np.float64) if query_features is not None
-             else self._query_features(np.asarray(data), np.asarray(data_err), rstate))
+             else self._draw_query(data, data_err, rstate, query_draws))
         obj = HostObjects(data, data_err, data_mask)
         Ndata = len(obj.x)
         pdfs = pinned_empty((Ndata, Nx))
@@ -579,13 +748,13 @@ class NearestNeighbors():
 
     def _fit_predict(self, data, data_err, data_mask, model_labels, model_label_errs, lprob_func=None,
                      rstate=None, label_dict=None, label_grid=None, kde_args=None, kde_kwargs=None,
-                     lprob_args=None, lprob_kwargs=None, track_scale=False, save_fits=True):
+                     lprob_args=None, lprob_kwargs=None, track_scale=False, save_fits=True, query_draws='host'):
         """Generator twin (knn.py:722-874); uses the ``k / eps / lp_norm / dbound`` attributes."""
         pdfs, (lmap, levid) = self.fit_predict(
             data, data_err, data_mask, model_labels, model_label_errs, lprob_func=lprob_func, rstate=rstate,
             k=self.k, eps=self.eps, lp_norm=self.lp_norm, distance_upper_bound=self.dbound,
             label_dict=label_dict, label_grid=label_grid, kde_args=kde_args, kde_kwargs=kde_kwargs,
             lprob_args=lprob_args, lprob_kwargs=lprob_kwargs, return_gof=True, track_scale=track_scale,
-            verbose=False, save_fits=save_fits)
+            verbose=False, save_fits=save_fits, query_draws=query_draws)
         for i in range(len(pdfs)):
             yield pdfs[i], (lmap[i], levid[i])

@@ -20,7 +20,9 @@ the compute.  What can be exchanged afterwards:
 
 For the k-NN variant the per-object Monte-Carlo draws are generated for ALL objects
 before sharding, so the random stream -- and therefore the result -- does not depend on
-the number of ranks.
+the number of ranks.  With ``query_draws='device'`` every rank takes the same Philox key from
+the caller's ``rstate`` and draws the rows it computes on its own GPU: a draw is a function of
+(key, global row, band), so the result is again the single-process call's.
 """
 import numpy as np
 
@@ -139,13 +141,22 @@ def _overlapped(fitter, data, data_err, data_mask, model_labels, model_label_err
              "return_gof", "save_fits", "verbose", "track_scale", "prepared"}
     search = {}
     if is_knn:
-        known |= {"k", "eps", "lp_norm", "distance_upper_bound", "query_features"}
+        known |= {"k", "eps", "lp_norm", "distance_upper_bound", "query_features", "query_draws"}
         search = {kk: kwargs[kk] for kk in ("k", "eps", "lp_norm", "distance_upper_bound") if kk in kwargs}
     extra = set(kwargs) - known
     if extra or kwargs.get("kde_args") or kwargs.get("lprob_args"):
         raise NotImplementedError("sharded_fit_predict (overlapped path): unsupported arguments %s" % sorted(extra))
     dQ = None
+    qkey = None
     if is_knn:
+        from .knn import _check_draws
+        _check_draws('query_draws', kwargs.get("query_draws", 'host'), kwargs.get("query_features"))
+    if is_knn and kwargs.get("query_draws", 'host') == 'device':
+        # one Philox key from the caller's rstate, the same on every rank (as the host draw below is): a draw is a function of
+        # (key, global row, band) alone, so each rank draws the rows it computes on its own GPU -- below, before the clean
+        qkey = (rstate if rstate is not None else np.random).randint(0, 2**32, size=2, dtype=np.uint32)
+        fitter.query_key = qkey
+    elif is_knn:
         # knn.py:830-832 for EVERY object before the objects are dealt out: the random stream -- and so the result -- does not
         # depend on the number of ranks.  (N x B values on the host; a driver that calls step after step passes them in.)
         q = kwargs.get("query_features")
@@ -165,11 +176,19 @@ def _overlapped(fitter, data, data_err, data_mask, model_labels, model_label_err
         # rank's copy ends up cleaned, as after the single-process call (N x B values: negligible)
         if not lib_stream:
             sync()                                                  # (stand-in fitters: the tensors are read on another stream)
-        if N:
-            eng.clean(dX, dXe, dXm)
         C = max(1, int(chunks))
         cs = max(1, -(-N // (world * C)))
         C = -(-N // (world * cs))                                   # rounds that hold at least one object
+        if qkey is not None:
+            # this rank's rows of every round, drawn from the objects as given (knn.py:830 draws before logprob cleans)
+            dQ = torch.empty((N, int(dX.shape[1])), dtype=torch.float64, device=dev)
+            for c in range(C):
+                lo = c * world * cs + rank * cs
+                hi = min(lo + cs, N)
+                if hi > lo:
+                    dQ[lo:hi] = fitter._device_features(dX[lo:hi], dXe[lo:hi], qkey, first=lo)
+        if N:
+            eng.clean(dX, dXe, dXm)
         rows = C * world * cs
         pdfs = torch.empty((rows, G), dtype=torch.float64, device=dev)
         lm = torch.empty(rows, dtype=torch.float64, device=dev)
@@ -269,7 +288,16 @@ def sharded_fit_predict(fitter, data, data_err, data_mask, model_labels, model_l
     sl = shard_slice(n, world, rank)
     kwargs = dict(kwargs, return_gof=True)
     kwargs.setdefault('verbose', False)
-    if hasattr(fitter, 'KDTrees'):
+    if hasattr(fitter, 'KDTrees') and kwargs.get('query_draws', 'host') != 'host':
+        from .knn import _check_draws
+        _check_draws('query_draws', kwargs['query_draws'], kwargs.get('query_features'))
+        # the key from the caller's rstate, the same on every rank; this rank's rows drawn on its GPU at their global row numbers
+        key = (rstate if rstate is not None else np.random).randint(0, 2**32, size=2, dtype=np.uint32)
+        fitter.query_key = key
+        kwargs.pop('query_draws')
+        kwargs['query_features'] = fitter.query_features(data[sl], data_err[sl], draws='device', key=key, first=sl.start)
+    elif hasattr(fitter, 'KDTrees'):
+        kwargs.pop('query_draws', None)
         if kwargs.get('query_features') is not None:
             kwargs['query_features'] = kwargs['query_features'][sl]         # drawn by the caller for every object
         else:

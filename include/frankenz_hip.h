@@ -562,6 +562,32 @@ int  fz_fit_sparse(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N, co
                    double lncut, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
                    int64_t* ndim, double* scale, double* scale_err, double* lmap, double* levid, double* lnkept);
 
+/* ---- Monte-Carlo draws of the k-NN fitter on the device (extension; docs/knn.md, knn.py:158-188 / 830-832) ----
+ * The reference draws its K feature sets (knn.py:158-188) and every object's query features (knn.py:830-832) with NumPy's normal and
+ * maps them to magnitudes / luptitudes.  Here the variates are Philox4x32-10: one call gives two standard normals by Box-Muller
+ * (u1 = 1 - U(words 0, 1), u2 = U(words 2, 3), r = sqrt(-2 ln u1), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2)) under the key
+ * (key0, key1 ^ 0x6B6E6D63) at the counter (row lo, row hi, band >> 1, set): an even band takes z0, an odd one z1; set 0 is a query
+ * draw of object `first + i`, set 1 + t feature set t of model j.  A draw is a function of (key, row, band, set) alone.  The law is the
+ * reference's, the realisation for a seed is not.
+ * fz_knn_map -- kind 0 identity, 1 magnitude (-2.5 log10(d / zeropoints)), 2 luptitude (-2.5 / ln 10 (asinh(d / (2 skynoise)) +
+ *   ln(skynoise / zeropoints))), with one fp64 constant per band.
+ * fz_knn_draw_features -- x, xe, q (N, F) float64, host or device, rows AS GIVEN (before any clean): q = map(fma(xe, z, x)) in fp64.
+ *   xe == 0 gives x; non-finite x follows IEEE arithmetic; a negative or nan xe: -4, naming the smallest such object.  N == 0: no launch.
+ * fz_knn_draw_trees -- models, models_err (M, F) float64, host or device (the shape of the uploaded models): set t, model j is
+ *   float32(map(double(float32(fma(ye, z, y))))) -- the reference's two float32 roundings, the map in fp64 between them -- and the K
+ *   sets become the resident sets exactly as fz_knn_upload_trees of the same floats makes them; feats_out (K, M, F) float32, host or
+ *   device, or NULL: a copy of them.  A negative or nan error: -4, nothing installed. */
+typedef struct fz_knn_map {
+    int32_t kind;               /* 0 identity, 1 magnitude, 2 luptitude */
+    int32_t reserved_;
+    double  skynoise[32];       /* per band (luptitude) */
+    double  zeropoints[32];     /* per band (magnitude, luptitude) */
+} fz_knn_map;
+int  fz_knn_draw_features(fz_ctx* ctx, const double* x, const double* xe, int64_t N, int32_t F, const fz_knn_map* map, uint32_t key0,
+                          uint32_t key1, int64_t first, double* q);
+int  fz_knn_draw_trees(fz_ctx* ctx, const double* models, const double* models_err, int32_t K, int64_t M, int32_t F,
+                       const fz_knn_map* map, uint32_t key0, uint32_t key1, float* feats_out /* may be NULL */);
+
 /* diagnostic: evaluate one of the library's device math helpers elementwise
  * (which: 0 v_rcp_f64 seed, 1 / 2 rcp with one / two Newton steps, 3 log_pos,
  * 4 exp_neg).  Used by tests to pin their accuracy against NumPy. */
