@@ -143,6 +143,10 @@ ABI = {
     "fz_mw_sweep": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, C.c_uint32, C.c_uint32, _I64, C.c_uint64, _P, _P]),
     "fz_mw_dirichlet": (C.c_int, [_P, _P, _P, _I64, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P]),
     "fz_mw_chain": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, C.c_uint32, C.c_uint32, _I64, C.c_uint64, _I32, _P, _P, _P]),
+    "fz_mw_em_index_bytes": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P]),
+    "fz_mw_em_index": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P]),
+    "fz_mw_loglike": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P]),
+    "fz_mw_em": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _I32, _P, _P, _P, _P]),
     "fz_sparsify_logwt": (C.c_int, [_P, _P, _I64, _I64, _I64, _F64] + [_P] * 6),
     "fz_fit_sparse": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _I64, _F64] + [_P] * 12),
     "fz_knn_draw_features": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(KnnMap), C.c_uint32, C.c_uint32, _I64, _P]),

@@ -502,6 +502,14 @@ class BruteForce():
             raise ValueError("Fits have not been computed.")
         return model_weight_sampler(self.fit_lnlike, device=self._device)
 
+    def weight_em(self):
+        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
+        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
+        from .samplers import model_weight_em
+        if self.fit_lnlike is None:
+            raise ValueError("Fits have not been computed.")
+        return model_weight_em(self.fit_lnlike, device=self._device)
+
     def fit_sparse(self, data, data_err, data_mask, Nkeep=256, wt_thresh=1e-3, lprob_func=None, lprob_args=None, lprob_kwargs=None,
                    track_scale=False, resident=False, verbose=True):
         """Extension (no reference counterpart; docs/sparse_fits.md): one exhaustive fit that leaves, per object, the exact ``Nkeep``

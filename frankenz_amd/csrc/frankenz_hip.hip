@@ -21,6 +21,7 @@
 #include "fz_synphot.h"
 #include "fz_draw.h"
 #include "fz_mw.h"
+#include "fz_mw_em.h"
 #include "fz_sparse.h"
 
 using namespace fz;
@@ -1244,6 +1245,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_draw_host.inc"
 #include "fz_sparse_host.inc"
 #include "fz_mw_host.inc"
+#include "fz_mw_em_host.inc"
 
 #ifdef FZ_KM_STATS
 extern "C" int fz_debug_kmstats(unsigned long long* out, int reset) {

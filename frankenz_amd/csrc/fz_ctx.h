@@ -141,6 +141,8 @@ struct fz_ctx {
     DevBuf d_draw[6];
     // model-weight sampler (fz_mw_host.inc): the error flags of a call; the block partials of sum(g) and their sum
     DevBuf d_mw[2];
+    // EM over the model weights (fz_mw_em_host.inc, which lists them)
+    DevBuf d_mwem[12];
     // sparse fits (fz_sparse_host.inc): lnkept, the kept ln-prob rows, the gathered rows of one plane at a time
     DevBuf d_sparse[3];
 
@@ -154,6 +156,7 @@ struct fz_ctx {
         for (auto& b : d_mc) v.push_back(&b);
         for (auto& b : d_draw) v.push_back(&b);
         for (auto& b : d_mw) v.push_back(&b);
+        for (auto& b : d_mwem) v.push_back(&b);
         for (auto& b : d_sparse) v.push_back(&b);
         return v;
     }

@@ -374,6 +374,31 @@ class Engine(object):
                                    int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF, int(first), int(sweep0), int(nsweeps), ptr(counts),
                                    ptr(pos), ptr(counts_all)))
 
+    # -- EM over model weights (docs/model_weights.md; fz_mw_em.h) ----------------
+    def mw_em_index_bytes(self, n, W, M, nnbr):
+        """fz_mw_em_index_bytes -> (entries, bytes) of the inverted index of these neighbour counts"""
+        e, b = C.c_int64(0), C.c_int64(0)
+        check(self.lib.fz_mw_em_index_bytes(self.h, int(n), int(W), ptr(nnbr), int(M), C.addressof(e), C.addressof(b)))
+        return int(e.value), int(b.value)
+
+    def mw_em_index(self, rows, n, W, M, neighbors, nnbr, entries, col_off, col_obj, col_val):
+        """fz_mw_em_index: device rows and tables -> ``col_off`` (M + 1) int64, ``col_obj`` (entries) int32, ``col_val`` (entries)"""
+        check(self.lib.fz_mw_em_index(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), int(entries), ptr(col_off),
+                                      ptr(col_obj), ptr(col_val)))
+
+    def mw_loglike(self, rows, n, W, M, lnw, neighbors=None, nnbr=None, ell=None):
+        """fz_mw_loglike -> (sum_i logsumexp_k (rows + lnw[neighbors])_ik over the rows with a posterior, rows skipped)"""
+        out, ns = np.zeros(1), np.zeros(1, dtype=np.int64)
+        check(self.lib.fz_mw_loglike(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(lnw), ptr(ell), ptr(out),
+                                     ptr(ns)))
+        return float(out[0]), int(ns[0])
+
+    def mw_em(self, rows, n, W, M, alpha, lnw, niter, pos, counts, trace, nskip, neighbors=None, nnbr=None, index=None, entries=0):
+        """fz_mw_em: ``niter`` EM iterations on device-resident rows (and ``index`` = (col_off, col_obj, col_val)); ``lnw`` in and out"""
+        co, cj, cv = index if index is not None else (None, None, None)
+        check(self.lib.fz_mw_em(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(co), ptr(cj), ptr(cv), int(entries),
+                                ptr(alpha), ptr(lnw), int(niter), ptr(pos), ptr(counts), ptr(trace), ptr(nskip)))
+
     # -- k-NN ------------------------------------------------------------
     def knn_upload_trees(self, feats, key=None):
         """``key``: the caller's content key of ``feats`` (``_digest``); an unchanged set is not sent (nor Morton-sorted) again"""

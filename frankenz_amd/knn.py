@@ -623,6 +623,15 @@ class NearestNeighbors():
         return model_weight_sampler(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
                                     device=self._device)
 
+    def weight_em(self):
+        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
+        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
+        from .samplers import model_weight_em
+        if self.fit_lnlike is None or getattr(self, "neighbors", None) is None:
+            raise ValueError("Fits have not been computed.")
+        return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
+                               device=self._device)
+
     # ------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None,
                 kde_args=None, kde_kwargs=None, return_gof=False, verbose=True):

@@ -3,7 +3,8 @@
 redshift-assignment step ``nz_assign``, the stacked n(z) ``stack_nz``, and the two MCMC drivers ``population_sampler``
 (Metropolis-Hastings-in-Gibbs over random pairs of bins) and ``hierarchical_sampler`` (Gibbs with a Dirichlet hyper-prior) with
 the reference's interface.  The PDF stack is uploaded once per sampler and stays on the device; nothing of the size of the
-catalogue crosses the bus inside a chain.  docs/samplers.md.
+catalogue crosses the bus inside a chain.  docs/samplers.md.  ``model_weight_sampler`` (Gibbs) and ``model_weight_em`` (EM: point estimate and
+marginal ln-likelihood) are the extension over the weights of the training objects themselves, docs/model_weights.md.
 """
 import sys
 
@@ -11,7 +12,8 @@ import numpy as np
 
 from .engine import get_engine
 
-__all__ = ["loglike_nz", "nz_assign", "stack_nz", "population_sampler", "hierarchical_sampler", "model_weight_sampler"]
+__all__ = ["loglike_nz", "nz_assign", "stack_nz", "population_sampler", "hierarchical_sampler", "model_weight_sampler",
+           "model_weight_em"]
 
 _NZ_SEGMENT = 8            # saved samples of the population chain per library call (the state stays on the device in between)
 
@@ -477,7 +479,162 @@ def _mw_lnpost(counts, pos, alpha):
     return lnlike + lnprior
 
 
-class model_weight_sampler(object):
+def _mw_fixed_sum(a):
+    """the sum of ``a`` in the order of ``k_mw_gsum`` (csrc/fz_mw.h): blocks of 256 summed by a halving tree, thread ``t`` of one block
+    adds the block sums ``t, t + 256, ...`` in order, then the same tree"""
+    def tree(v):                                    # (..., 256) -> (...)
+        n = 256
+        while n > 1:
+            n //= 2
+            v = v[..., :n] + v[..., n:2 * n]
+        return v[..., 0]
+    a = np.asarray(a, dtype=np.float64)
+    nblk = (len(a) + 255) // 256
+    pad = np.zeros(nblk * 256); pad[:len(a)] = a
+    part = tree(pad.reshape(nblk, 256))
+    acc = np.zeros(256)
+    for k in range(0, nblk, 256):
+        acc[:len(part[k:k + 256])] += part[k:k + 256]
+    return float(tree(acc))
+
+
+def _mw_em_lnw(w, M):
+    """``ln w - ln sum(w)`` (the fixed-order sum) of a weight vector that is finite, non-negative and has a positive sum"""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (M,) or not np.isfinite(w).all() or (w < 0.).any() or not w.sum() > 0.:
+        raise ValueError("`w` must hold one finite non-negative weight per model, with a positive sum")
+    with np.errstate(divide='ignore'):
+        return np.log(w) - np.log(_mw_fixed_sum(w))
+
+
+class _model_weight_rows(object):
+    """What ``model_weight_sampler`` and ``model_weight_em`` share: the checks of the rows, their one upload, the marginal
+    ln-likelihood of a weight vector and what the weights are for (``logwt``, ``population_pdfs``)."""
+
+    def __init__(self, lnlike, neighbors=None, Nneighbors=None, Nmodels=None, device=None):
+        if (neighbors is None) != (Nneighbors is None):
+            raise ValueError("`neighbors` and `Nneighbors` come together")
+        if len(lnlike.shape) != 2:
+            raise ValueError("`lnlike` must have shape (Nobj, Nmodels) or (Nobj, K*k)")
+        N, W = (int(v) for v in lnlike.shape)
+        if neighbors is None:
+            if Nmodels is not None and int(Nmodels) != W:
+                raise ValueError("dense rows have one entry per model")
+            Nmodels = W
+        else:
+            if Nmodels is None:
+                raise ValueError("`Nmodels` must be given beside `neighbors`")
+            if tuple(neighbors.shape) != (N, W) or tuple(Nneighbors.shape) != (N,):
+                raise ValueError("`neighbors` must have the shape of `lnlike` and `Nneighbors` one entry per object")
+        if N < 1 or W < 1 or int(Nmodels) < 1:
+            raise ValueError("the sampler needs at least one object and one model")
+        self.lnlike, self.neighbors, self.Nneighbors = lnlike, neighbors, Nneighbors
+        self.NOBJ, self.W, self.NMODEL = N, W, int(Nmodels)
+        self.device = device
+        self._dev = None
+
+    def _resident(self, eng):
+        """the rows (and neighbour tables) on the engine's GPU: uploaded once, or the caller's device arrays themselves"""
+        if self._dev is not None:
+            return self._dev
+        # only what is UPLOADED needs room: arrays already on the device are used where they lie
+        parts = [a for a in (self.lnlike, self.neighbors, self.Nneighbors) if isinstance(a, np.ndarray)]
+        need = sum(int(a.size) * 8 for a in parts)
+        if need > eng.workspace_limit():
+            raise MemoryError("%s: the rows need %d bytes of device memory, the workspace limit is %d (nothing is "
+                              "spilled)" % (type(self).__name__, need, eng.workspace_limit()))
+
+        def put(a, dt):
+            if a is None:
+                return None
+            if isinstance(a, np.ndarray):
+                try:
+                    return eng.device_array(np.ascontiguousarray(a, dtype=dt))
+                except MemoryError:
+                    raise MemoryError("%s: the rows need %d bytes of device memory" % (type(self).__name__, need))
+            if not hasattr(a, "data_ptr"):
+                raise TypeError("rows must be NumPy arrays or arrays on the GPU")
+            # a device array is read as raw C-contiguous memory of 8-byte items: anything else is refused
+            if hasattr(a, "element_size") and a.element_size() != 8:
+                raise TypeError("device rows must be float64 and device neighbour tables int64")
+            kind = getattr(a, "dtype", None)
+            if kind is not None and not str(kind).endswith(np.dtype(dt).name):
+                raise TypeError("a device array of dtype %s where %s is needed" % (kind, np.dtype(dt).name))
+            if hasattr(a, "is_contiguous") and not a.is_contiguous():
+                raise ValueError("device arrays must be C-contiguous (a strided view would be read as raw memory)")
+            return a
+
+        self._dev = (put(self.lnlike, np.float64), put(self.neighbors, np.int64), put(self.Nneighbors, np.int64))
+        return self._dev
+
+    def _marginal(self, w):
+        """(sum_i ln sum_j L_ij w_j over the objects with a posterior, objects skipped) for one weight vector, normalised with the
+        fixed-order sum: one ``fz_mw_loglike`` call on the rows where they are (host rows are staged in chunks, no index is built)"""
+        lnw = _mw_em_lnw(self._weights(w), self.NMODEL)
+        eng = get_engine(self.device)
+        rows, nb, nn = self._dev if self._dev is not None else (self.lnlike, self.neighbors, self.Nneighbors)
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            nb = None if nb is None else np.ascontiguousarray(nb, dtype=np.int64)
+            nn = None if nn is None else np.ascontiguousarray(nn, dtype=np.int64)
+        return eng.mw_loglike(rows, self.NOBJ, self.W, self.NMODEL, lnw, neighbors=nb, nnbr=nn)
+
+    # ---- what the weights are for -------------------------------------------------------------------------------------------------
+    def _weights(self, w):
+        if w is None:
+            w = self._default_weights(False)
+        w = np.asarray(w, dtype=np.float64)
+        if w.shape[-1] != self.NMODEL:
+            raise ValueError("`w` must have one entry per model")
+        return w
+
+    def logwt(self, w=None):
+        """``(N, W)`` rows ``lnlike + ln w[neighbors]`` (dense: ``lnlike + ln w``): the objects' ln-posterior rows under the inferred
+        population, for the fitter's ``predict(logwt=)`` / ``sample(logwt=)``.  ``w`` defaults to the mean of the samples.  Entries
+        past ``Nneighbors[i]`` keep the row's own padding.  NumPy, or torch when the rows are tensors."""
+        w = self._weights(w)
+        if w.ndim != 1:
+            raise ValueError("`w` must be one weight vector")
+        with np.errstate(divide='ignore'):
+            lnw = np.log(w)
+        if _is_torch(self.lnlike):
+            import torch
+            r = self.lnlike
+            t = torch.as_tensor(lnw, dtype=r.dtype, device=r.device)
+            if self.neighbors is None:
+                return r + t[None, :]
+            nb, nn = torch.as_tensor(self.neighbors, device=r.device), torch.as_tensor(self.Nneighbors, device=r.device)
+            valid = torch.arange(self.W, device=r.device)[None, :] < nn[:, None]
+            return torch.where(valid, r + t[torch.where(valid, nb, torch.zeros_like(nb))], r)
+        r = np.asarray(_mw_host(self.lnlike), dtype=np.float64)
+        if self.neighbors is None:
+            return r + lnw[None, :]
+        nb, nn = _mw_host(self.neighbors), np.asarray(_mw_host(self.Nneighbors))
+        valid = np.arange(self.W)[None, :] < nn[:, None]
+        with np.errstate(invalid='ignore'):
+            return np.where(valid, r + lnw[np.where(valid, nb, 0)], r)
+
+    def population_pdfs(self, model_labels, model_label_errs, label_dict=None, label_grid=None, kde_kwargs=None, w=None):
+        """The weight samples as population distributions of a label: ``(Niter, G)`` n(label) samples, row ``s`` the KDE of the
+        models' labels weighted by ``w[s]`` (the reference's ``gauss_kde_dict`` / ``gauss_kde`` with ``y_wt = w[s]``, normalised
+        unless ``kde_kwargs`` says otherwise).  ``w`` defaults to all the samples.  The KDE clips weights below ``wt_thresh`` (1e-3)
+        of the largest: pass ``kde_kwargs={'wt_thresh': 0}`` if no weight is to be clipped."""
+        from .engine import kde_opts
+        if label_dict is None and label_grid is None:
+            raise ValueError("`label_dict` or `label_grid` must be specified.")
+        w = self._default_weights(True) if w is None else self._weights(w)
+        w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
+        if w.shape[1] != self.NMODEL or len(model_labels) != self.NMODEL:
+            raise ValueError("`w` and the labels must have one entry per model")
+        eng = get_engine(self.device)
+        Nx = eng.set_labels(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs)
+        pdfs = np.empty((len(w), Nx))
+        if len(w):
+            eng.predict_logwt(w, kde_opts(kde_kwargs), pdfs, is_log=False, n=len(w))
+        return pdfs
+
+
+class model_weight_sampler(_model_weight_rows):
     """
     Hierarchical re-weighting of a training set: Gibbs sampling of population weights ``w`` over the ``M`` training objects (models)
     under a Dirichlet hyper-prior, given every object's ln-likelihood rows.  The law is the reference's ``hierarchical_sampler``
@@ -503,30 +660,11 @@ class model_weight_sampler(object):
     """
 
     def __init__(self, lnlike, neighbors=None, Nneighbors=None, Nmodels=None, device=None):
-        if (neighbors is None) != (Nneighbors is None):
-            raise ValueError("`neighbors` and `Nneighbors` come together")
-        if len(lnlike.shape) != 2:
-            raise ValueError("`lnlike` must have shape (Nobj, Nmodels) or (Nobj, K*k)")
-        N, W = (int(v) for v in lnlike.shape)
-        if neighbors is None:
-            if Nmodels is not None and int(Nmodels) != W:
-                raise ValueError("dense rows have one entry per model")
-            Nmodels = W
-        else:
-            if Nmodels is None:
-                raise ValueError("`Nmodels` must be given beside `neighbors`")
-            if tuple(neighbors.shape) != (N, W) or tuple(Nneighbors.shape) != (N,):
-                raise ValueError("`neighbors` must have the shape of `lnlike` and `Nneighbors` one entry per object")
-        if N < 1 or W < 1 or int(Nmodels) < 1:
-            raise ValueError("the sampler needs at least one object and one model")
-        self.lnlike, self.neighbors, self.Nneighbors = lnlike, neighbors, Nneighbors
-        self.NOBJ, self.W, self.NMODEL = N, W, int(Nmodels)
-        self.device = device
+        _model_weight_rows.__init__(self, lnlike, neighbors, Nneighbors, Nmodels, device)
         self.samples = []
         self.samples_lnp = []
         self.sweep_counts = []
         self.philox_key = None
-        self._dev = None
 
     def reset(self):
         """Re-initialize the sampler."""
@@ -537,40 +675,6 @@ class model_weight_sampler(object):
     def results(self):
         """Return samples: ``(samples (Niter, M), samples_lnp (Niter))``."""
         return np.array(self.samples), np.array(self.samples_lnp)
-
-    def _resident(self, eng):
-        """the rows (and neighbour tables) on the engine's GPU: uploaded once, or the caller's device arrays themselves"""
-        if self._dev is not None:
-            return self._dev
-        # only what is UPLOADED needs room: arrays already on the device are used where they lie
-        parts = [a for a in (self.lnlike, self.neighbors, self.Nneighbors) if isinstance(a, np.ndarray)]
-        need = sum(int(a.size) * 8 for a in parts)
-        if need > eng.workspace_limit():
-            raise MemoryError("model_weight_sampler: the rows need %d bytes of device memory, the workspace limit is %d (nothing is "
-                              "spilled)" % (need, eng.workspace_limit()))
-
-        def put(a, dt):
-            if a is None:
-                return None
-            if isinstance(a, np.ndarray):
-                try:
-                    return eng.device_array(np.ascontiguousarray(a, dtype=dt))
-                except MemoryError:
-                    raise MemoryError("model_weight_sampler: the rows need %d bytes of device memory" % need)
-            if not hasattr(a, "data_ptr"):
-                raise TypeError("rows must be NumPy arrays or arrays on the GPU")
-            # a device array is read as raw C-contiguous memory of 8-byte items: anything else is refused
-            if hasattr(a, "element_size") and a.element_size() != 8:
-                raise TypeError("device rows must be float64 and device neighbour tables int64")
-            kind = getattr(a, "dtype", None)
-            if kind is not None and not str(kind).endswith(np.dtype(dt).name):
-                raise TypeError("a device array of dtype %s where %s is needed" % (kind, np.dtype(dt).name))
-            if hasattr(a, "is_contiguous") and not a.is_contiguous():
-                raise ValueError("device arrays must be C-contiguous (a strided view would be read as raw memory)")
-            return a
-
-        self._dev = (put(self.lnlike, np.float64), put(self.neighbors, np.int64), put(self.Nneighbors, np.int64))
-        return self._dev
 
     def _stack_start(self):
         """the analogue of ``stack_nz``: ``pos_j`` proportional to ``sum_i exp(r_ij - logsumexp_j' r_ij')``, a scatter-add of the
@@ -662,58 +766,128 @@ class model_weight_sampler(object):
             self.sweep_counts.extend(call)
             yield pos.copy(), _mw_lnpost(counts, pos, alpha)
 
-    # ---- what the weights are for -------------------------------------------------------------------------------------------------
-    def _weights(self, w):
-        if w is None:
-            if not len(self.samples):
-                raise ValueError("no samples yet: run the sampler or give `w`")
-            w = np.mean(self.samples, axis=0)
-        w = np.asarray(w, dtype=np.float64)
-        if w.shape[-1] != self.NMODEL:
-            raise ValueError("`w` must have one entry per model")
-        return w
+    def _default_weights(self, many):
+        if many:
+            return np.array(self.samples)
+        if not len(self.samples):
+            raise ValueError("no samples yet: run the sampler or give `w`")
+        return np.mean(self.samples, axis=0)
 
-    def logwt(self, w=None):
-        """``(N, W)`` rows ``lnlike + ln w[neighbors]`` (dense: ``lnlike + ln w``): the objects' ln-posterior rows under the inferred
-        population, for the fitter's ``predict(logwt=)`` / ``sample(logwt=)``.  ``w`` defaults to the mean of the samples.  Entries
-        past ``Nneighbors[i]`` keep the row's own padding.  NumPy, or torch when the rows are tensors."""
-        w = self._weights(w)
-        if w.ndim != 1:
-            raise ValueError("`w` must be one weight vector")
-        with np.errstate(divide='ignore'):
-            lnw = np.log(w)
-        if _is_torch(self.lnlike):
-            import torch
-            r = self.lnlike
-            t = torch.as_tensor(lnw, dtype=r.dtype, device=r.device)
-            if self.neighbors is None:
-                return r + t[None, :]
-            nb, nn = torch.as_tensor(self.neighbors, device=r.device), torch.as_tensor(self.Nneighbors, device=r.device)
-            valid = torch.arange(self.W, device=r.device)[None, :] < nn[:, None]
-            return torch.where(valid, r + t[torch.where(valid, nb, torch.zeros_like(nb))], r)
-        r = np.asarray(_mw_host(self.lnlike), dtype=np.float64)
-        if self.neighbors is None:
-            return r + lnw[None, :]
-        nb, nn = _mw_host(self.neighbors), np.asarray(_mw_host(self.Nneighbors))
-        valid = np.arange(self.W)[None, :] < nn[:, None]
-        with np.errstate(invalid='ignore'):
-            return np.where(valid, r + lnw[np.where(valid, nb, 0)], r)
+    def marginal_lnlike(self, w=None):
+        """``(lnlike, nskip)``: the marginal ln-likelihood ``sum_i ln sum_j L_ij w_j`` of one weight vector (default: the mean of the
+        samples) over the objects with a posterior under it, and how many have none -- ``model_weight_em.loglike``, one
+        ``fz_mw_loglike`` call.  Unlike ``samples_lnp`` it does not depend on a draw."""
+        return self._marginal(w)
 
-    def population_pdfs(self, model_labels, model_label_errs, label_dict=None, label_grid=None, kde_kwargs=None, w=None):
-        """The weight samples as population distributions of a label: ``(Niter, G)`` n(label) samples, row ``s`` the KDE of the
-        models' labels weighted by ``w[s]`` (the reference's ``gauss_kde_dict`` / ``gauss_kde`` with ``y_wt = w[s]``, normalised
-        unless ``kde_kwargs`` says otherwise).  ``w`` defaults to all the samples.  The KDE clips weights below ``wt_thresh`` (1e-3)
-        of the largest: pass ``kde_kwargs={'wt_thresh': 0}`` if no weight is to be clipped."""
-        from .engine import kde_opts
-        if label_dict is None and label_grid is None:
-            raise ValueError("`label_dict` or `label_grid` must be specified.")
-        w = np.array(self.samples) if w is None else self._weights(w)
-        w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
-        if w.shape[1] != self.NMODEL or len(model_labels) != self.NMODEL:
-            raise ValueError("`w` and the labels must have one entry per model")
+
+# ---- EM over the weights of the training objects (docs/model_weights.md, "EM") ------------------------------------------------------
+class model_weight_em(_model_weight_rows):
+    """
+    Maximum-likelihood / MAP population weights ``w`` over the ``M`` training objects by expectation-maximisation, and the marginal
+    ln-likelihood ``L(w) = sum_i ln sum_j L_ij w_j`` of any weight vector: the expectation form of ``model_weight_sampler``'s Gibbs
+    sweep (the reference's ``hierarchical_sampler``, samplers.py:311-535, with every entry's responsibility added where the sweep
+    draws one and counts).  Arguments, checks and the one upload of the rows are ``model_weight_sampler``'s.
+
+    One iteration from ``w``: ``ell_i = logsumexp_k (lnlike_ik + ln w[nbr_ik])``; ``lnpost = sum_i ell_i + sum_j (alpha_j - 1) ln w_j``;
+    ``c_j = sum exp(lnlike_ik + ln w_j - ell_i)`` over the entries of model ``j``; ``w'_j`` proportional to ``c_j + (alpha_j - 1)``.
+    ``alpha`` must be finite and ``>= 1`` (below 1 there is no maximum).  An object without a posterior under ``w`` (a nan, a maximum
+    that is not finite, no neighbour) is skipped and counted.  Every sum has one fixed order: a result is a function of its inputs.
+
+    Sparse rows are read a second time through an inverted index (per model the entries that list it, in object order), built on the
+    device at the first ``step`` / ``run`` and kept: 12 bytes per counted entry, which must fit the workspace limit
+    (``MemoryError`` names them).  ``loglike`` needs neither the index nor resident rows.
+    """
+
+    def __init__(self, lnlike, neighbors=None, Nneighbors=None, Nmodels=None, device=None):
+        _model_weight_rows.__init__(self, lnlike, neighbors, Nneighbors, Nmodels, device)
+        self.pos = self.lnw = self.counts = None
+        self.lnpost_trace = np.zeros(0)
+        self.nskip_trace = np.zeros(0, dtype=np.int64)
+        self.niter = 0
+        self.converged = False
+        self._index = None
+
+    def _default_weights(self, many):
+        if self.pos is None:
+            raise ValueError("no weights yet: run the iteration or give `w`")
+        return self.pos
+
+    def _alpha(self, alpha):
+        M = self.NMODEL
+        alpha = np.ones(M) if alpha is None else np.ascontiguousarray(alpha, dtype=np.float64)
+        if alpha.shape != (M,) or np.any(~np.isfinite(alpha) | (alpha < 1.)):
+            raise ValueError("`alpha` must hold one finite entry >= 1 per model (below 1 the posterior has no maximum)")
+        return alpha
+
+    def loglike(self, w=None):
+        """``(lnlike, nskip)``: ``sum_i ln sum_j L_ij w_j`` over the objects with a posterior under ``w`` (default ``pos``), and
+        the number of objects without one."""
+        return self._marginal(w)
+
+    def _problem(self, eng):
+        """the resident rows and, for sparse rows, the inverted index (built once)"""
+        d_rows, d_nb, d_nn = self._resident(eng)
+        if d_nb is not None and self._index is None:
+            N, W, M = self.NOBJ, self.W, self.NMODEL
+            E, nbytes = eng.mw_em_index_bytes(N, W, M, d_nn)
+            if nbytes > eng.workspace_limit():
+                raise MemoryError("model_weight_em: the inverted index needs %d bytes of device memory, the workspace limit is %d "
+                                  "(nothing is spilled)" % (nbytes, eng.workspace_limit()))
+            from .engine import DeviceArray
+            try:
+                idx = (DeviceArray(eng, (M + 1,), np.int64), DeviceArray(eng, (max(E, 1),), np.int32),
+                       DeviceArray(eng, (max(E, 1),), np.float64))
+            except MemoryError:
+                raise MemoryError("model_weight_em: the inverted index needs %d bytes of device memory" % nbytes)
+            eng.mw_em_index(d_rows, N, W, M, d_nb, d_nn, E, *idx)
+            self._index = (E, idx)
+        return d_rows, d_nb, d_nn
+
+    def _iterate(self, eng, d_alpha, d_lnw, niter):
+        """``niter`` iterations in ONE library call -> (pos, counts, trace (niter), nskip (niter)); ``d_lnw`` moves on"""
+        N, W, M = self.NOBJ, self.W, self.NMODEL
+        d_rows, d_nb, d_nn = self._problem(eng)
+        E, idx = self._index if self._index is not None else (0, None)
+        pos, counts = np.empty(M), np.empty(M)
+        trace, nskip = np.empty(niter), np.empty(niter, dtype=np.int64)
+        eng.mw_em(d_rows, N, W, M, d_alpha, d_lnw, niter, pos, counts, trace, nskip, neighbors=d_nb, nnbr=d_nn, index=idx, entries=E)
+        return pos, counts, trace, nskip
+
+    def step(self, w, alpha=None):
+        """One iteration from ``w`` -> ``(w_new, lnpost_of_w, counts)``: the ln-posterior is that of ``w`` itself, ``counts`` the
+        expected counts ``c`` under it (``counts.sum()`` is the number of objects with a posterior)."""
+        alpha = self._alpha(alpha)
+        lnw = _mw_em_lnw(w, self.NMODEL)
         eng = get_engine(self.device)
-        Nx = eng.set_labels(model_labels, model_label_errs, label_dict, label_grid, kde_kwargs)
-        pdfs = np.empty((len(w), Nx))
-        if len(w):
-            eng.predict_logwt(w, kde_opts(kde_kwargs), pdfs, is_log=False, n=len(w))
-        return pdfs
+        pos, counts, trace, _ = self._iterate(eng, alpha, eng.device_array(lnw), 1)
+        return pos, float(trace[0]), counts
+
+    def run(self, maxiter=500, alpha=None, pos_init=None, tol=1e-6, check_every=10, verbose=True):
+        """Iterate from ``pos_init`` (default: uniform weights) until the ln-posterior grows by at most ``tol`` nats in one
+        iteration, or ``maxiter`` iterations.  One library call runs ``check_every`` iterations without a host synchronisation;
+        the trace is read after each call, so the iteration stops at the end of the call in which the increase first fell to
+        ``tol``.  Sets ``pos``, ``lnw``, ``counts`` (of the last iteration), ``lnpost_trace[t]`` (the ln-posterior of the weights
+        going into iteration ``t``), ``nskip_trace``, ``niter`` and ``converged``.  Returns ``pos``."""
+        maxiter, check_every, M = int(maxiter), int(check_every), self.NMODEL
+        if maxiter < 1 or check_every < 1:
+            raise ValueError("`maxiter` and `check_every` must be at least 1")
+        alpha = self._alpha(alpha)
+        lnw0 = np.full(M, -np.log(float(M))) if pos_init is None else _mw_em_lnw(pos_init, M)
+        eng = get_engine(self.device)
+        d_alpha, d_lnw = eng.device_array(alpha), eng.device_array(lnw0)
+        traces, skips, done, last = [], [], 0, None
+        self.converged = False
+        while done < maxiter and not self.converged:
+            n = min(check_every, maxiter - done)
+            pos, counts, trace, nskip = self._iterate(eng, d_alpha, d_lnw, n)
+            inc = np.diff(np.concatenate(([last] if last is not None else [], trace)))
+            self.converged = bool((inc <= tol).any())
+            traces.append(trace); skips.append(nskip)
+            done += n
+            last = trace[-1]
+            if verbose:
+                sys.stderr.write('\r Iteration {:d}/{:d} [lnpost = {:6.3f}]      '.format(done, maxiter, last))
+                sys.stderr.flush()
+        self.pos, self.counts, self.lnw = pos, counts, d_lnw.numpy()
+        self.lnpost_trace, self.nskip_trace, self.niter = np.concatenate(traces), np.concatenate(skips), done
+        return self.pos

@@ -106,3 +106,12 @@ class SparseFits(object):
             raise ValueError("the ln-likelihood rows were not kept")
         return model_weight_sampler(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
                                     device=self._device)
+
+    def weight_em(self):
+        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
+        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
+        from .samplers import model_weight_em
+        if self.fit_lnlike is None:
+            raise ValueError("the ln-likelihood rows were not kept")
+        return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
+                               device=self._device)

@@ -540,6 +540,37 @@ int  fz_mw_chain(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const in
                  const double* alpha, double* lnw, uint32_t key0, uint32_t key1, int64_t first, uint64_t sweep0, int32_t nsweeps,
                  int64_t* counts, double* pos, int64_t* counts_all);
 
+/* ---- EM over the model weights: point estimate and marginal ln-likelihood (extension; docs/model_weights.md, "EM") ----
+ * The expectation form of the sweep above, i.e. of the reference's hierarchical_sampler (samplers.py:311-535) over the model set:
+ * where fz_mw_sweep draws j_i ~ exp(rows_ij) w_j and counts, an iteration adds every entry's responsibility.  From lnw:
+ *   ell_i = logsumexp_k (rows_ik + lnw[nbr_ik]) over the counted entries, bit for bit the levid of fz_draw_logwt on the pre-added row;
+ *           a row without a posterior (the sweep's rule) is skipped: ell_i = nan, it adds to nothing and is counted in nskip.
+ *   lnpost = sum_i ell_i (block partials in index order) + sum_{j: alpha_j != 1} (alpha_j - 1) lnw_j
+ *   c_j    = sum over the counted entries with nbr_ik = j of exp((rows_ik + lnw_j) - ell_i), column j of the inverted index in
+ *           segments of 1024 entries (FZ_MW_EM_CSEG; dense rows: strips of 1024 objects), segment sums added in order
+ *   a_j    = c_j + (alpha_j - 1);  pos = a / sum(a);  lnw = log(a) - log(sum(a))      (sum(a) in the order of fz_mw_dirichlet's sum)
+ * No float atomics: every result is a function of its inputs alone.  Refusals: those of fz_mw_sweep; N >= 2^31 (FZ_MW_EM_NMAX): -5;
+ * alpha_j < 1 or not finite: -4 (no maximum); sum(a) == 0 (every object skipped at alpha == 1): -7.
+ *
+ * fz_mw_em_index_bytes -- nnbr (N), host or device (NULL: dense rows, no index): entries = sum(nnbr), bytes = what col_off (M + 1)
+ *   int64, col_obj (entries) int32 and col_val (entries) float64 need together.  The caller allocates.
+ * fz_mw_em_index -- device-resident rows, neighbors, nnbr -> the inverted index: column j's slice [col_off[j], col_off[j + 1]) lists the
+ *   counted entries with neighbour j in ascending (i, k) order, the object index and a copy of the row value (a stable LSD counting
+ *   sort by model index).  A bad table is refused (-3) before anything is gathered.
+ * fz_mw_loglike -- rows, neighbors, nnbr host or device (staged in chunks from the workspace limit as fz_mw_sweep), lnw (M) ->
+ *   ell (N) or NULL, lnlike (one double: sum of ell), nskip (one int64).  Needs no index; the same bits whatever the chunking.
+ * fz_mw_em -- niter iterations back to back without a host synchronisation inside, on device-resident rows and index (dense rows:
+ *   col_* NULL, entries 0).  lnw (M) in and out; pos (M) and counts (M, float64: c) of the last iteration; trace (niter): lnpost of
+ *   the weights going INTO each iteration; nskip (niter).  Bit for bit niter calls with niter = 1. */
+int  fz_mw_em_index_bytes(fz_ctx* ctx, int64_t N, int64_t W, const int64_t* nnbr, int64_t M, int64_t* entries, int64_t* bytes);
+int  fz_mw_em_index(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                    int64_t entries, int64_t* col_off, int32_t* col_obj, double* col_val);
+int  fz_mw_loglike(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                   const double* lnw, double* ell, double* lnlike, int64_t* nskip);
+int  fz_mw_em(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+              const int64_t* col_off, const int32_t* col_obj, const double* col_val, int64_t entries, const double* alpha, double* lnw,
+              int32_t niter, double* pos, double* counts, double* trace, int64_t* nskip);
+
 /* ---- sparse rows out of an exhaustive fit (extension, no reference counterpart; docs/sparse_fits.md) ----
  * For a row r[0..L) of ln-weights, a cap W >= 1 and a cut lncut < 0 (-inf allowed): a nan among the entries, or a max that is not
  * finite, keeps nothing (Nneighbors = 0).  Else m = max r, entry j is eligible iff r_j - m > lncut (one IEEE subtraction, strict), and
