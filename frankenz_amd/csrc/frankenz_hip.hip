@@ -720,10 +720,11 @@ static int run_fitpredict(fz_ctx* c, int mode, int var, int dp, int64_t n, const
     const fz_bt_table* t = bt_lookup(c);
     return t ? t->fitpredict(c, mode, var, dp, n, ko, lmap, levid, pdfs) : -5;
 }
-static int run_modec(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr = nullptr,
+// lnl_final: nullptr, or in: only the final ln-like plane is wanted / out: the kernel wrote it in its final form (no modec_final pass)
+static int run_modec(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, bool* lnl_final, const int64_t* nbr = nullptr,
                      const int64_t* nnb = nullptr, int W = 0) {
     const fz_bt_table* t = bt_lookup(c);
-    return t ? t->modec(c, var, n, o, nbr, nnb, W) : -5;
+    return t ? t->modec(c, var, n, o, nbr, nnb, W, lnl_final) : -5;
 }
 
 static int check_kde_opts(const fz_kde_opts* ko) {
@@ -892,6 +893,47 @@ static int prior_add(fz_ctx* c, const double* lnl, int64_t n, int64_t L, const i
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// the chunk driver behind fit, fit_predict, fit_draw, fit_sparse and the k-NN subset fit
+// ---------------------------------------------------------------------------
+// objects [i0, i0 + n) in chunks of nc: staged, cleaned and derived, c->prior pointed at them, then body(i0, n, var, flags)
+template <class Body>
+static int for_chunks(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, int64_t nc, const fz_like_opts* o, const PriorBind& pb,
+                      Body body) {
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t n = std::min(nc, N - i0);
+        ObjChunk ch; int fl = 0;
+        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
+        FZCHK(prior_chunk(c, pb, i0, n, c->M));
+        FZCHK(body(i0, n, pick_var(c, fl), fl));
+    }
+    return 0;
+}
+// the planes of a prepared chunk over the whole model set (nullptr: not wanted; lnprob may alias lnl): mode C or run_planes, then the
+// ln-prior.  lnl_final: as for run_modec
+struct Planes { double *lnl = nullptr, *chi2 = nullptr; int64_t* ndim = nullptr; double *scale = nullptr, *serr = nullptr, *lnprior = nullptr, *lnprob = nullptr; };
+static int chunk_planes(fz_ctx* c, int mode, int var, int64_t n, const fz_like_opts* o, const Planes& p, bool* lnl_final = nullptr) {
+    if (mode == 3) {
+        FZCHK(run_modec(c, var, n, o, lnl_final));
+        if (!(lnl_final && *lnl_final)) FZCHK(modec_final(c, n, var != VAR_FAST, o, p.lnl, p.chi2, p.ndim, p.scale, p.serr));
+    } else {
+        FZCHK(run_planes(c, mode, var, o->dim_prior, n, p.lnl, p.chi2, p.ndim, p.scale, p.serr));
+    }
+    return prior_add(c, p.lnl, n, c->M, nullptr, nullptr, p.lnprior, p.lnprob);
+}
+// ... its ln-prob rows only, in a plane of the context's: mode C's ln-like state plane (finished in place, by the iteration kernel
+// itself where it can: *in_kernel), else d_pl[0]; the ln-prior is added in place
+static int chunk_lnprob_rows(fz_ctx* c, int mode, int var, int64_t n, const fz_like_opts* o, double** rows, bool* in_kernel) {
+    DevBuf& buf = mode == 3 ? c->d_mc[1] : c->d_pl[0];
+    FZCHK(buf.ensure((size_t)n * c->M * 8));
+    Planes p; p.lnl = buf.as<double>();
+    if (c->prior.tab) p.lnprob = p.lnl;
+    *in_kernel = mode == 3;
+    FZCHK(chunk_planes(c, mode, var, n, o, p, in_kernel));
+    *rows = p.lnl;
+    return 0;
+}
+
 // The (P, M) table of an interpolated prior from a (P, NZ, NT) base table: see k_prior_rows_from_grid and include/frankenz_hip.h
 extern "C" int fz_prior_rows_from_grid(fz_ctx* c, const double* base, int64_t P, int64_t NZ, int64_t NT, const int32_t* iz,
                                        const double* g, const int32_t* t, int64_t M, double* table) {
@@ -955,30 +997,20 @@ extern "C" int fz_fit_prior_lerp(fz_ctx* c, double* x, double* xe, double* xm, i
     const int64_t per_obj = row * (nstage + (mode == 3 ? 4 : 0)) + pb.chunk_bytes_per_obj;
     int64_t nc = per_obj ? std::max<int64_t>(1, c->ws_limit / per_obj) : N;
     nc = std::min<int64_t>(std::min<int64_t>(nc, N), 1 << 18);
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        ObjChunk ch; int fl = 0;
-        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
-        FZCHK(prior_chunk(c, pb, i0, n, M));
-        const int var = pick_var(c, fl);
-        const bool masked = var != VAR_FAST;
+    FZCHK(for_chunks(c, x, xe, xm, N, nc, o, pb, [&](int64_t i0, int64_t n, int var, int) -> int {
         void* dst[NO];
         for (int k = 0; k < NO; ++k) {
             if (!outs[k] && !(k == 0 && need_lnl)) dst[k] = nullptr;
             else if (outs[k] && dev_out[k]) dst[k] = (char*)outs[k] + (size_t)i0 * row;
             else { FZCHK(c->d_pl[k].ensure((size_t)n * row)); dst[k] = c->d_pl[k].p; }
         }
-        if (mode == 3) {
-            FZCHK(run_modec(c, var, n, o));
-            FZCHK(modec_final(c, n, masked, o, (double*)dst[0], (double*)dst[1], (int64_t*)dst[2], (double*)dst[3], (double*)dst[4]));
-        } else {
-            FZCHK(run_planes(c, mode, var, o->dim_prior, n, (double*)dst[0], (double*)dst[1], (int64_t*)dst[2], (double*)dst[3],
-                             (double*)dst[4]));
-        }
-        FZCHK(prior_add(c, (const double*)dst[0], n, M, nullptr, nullptr, (double*)dst[5], (double*)dst[6]));
+        Planes p; p.lnl = (double*)dst[0]; p.chi2 = (double*)dst[1]; p.ndim = (int64_t*)dst[2]; p.scale = (double*)dst[3];
+        p.serr = (double*)dst[4]; p.lnprior = (double*)dst[5]; p.lnprob = (double*)dst[6];
+        FZCHK(chunk_planes(c, mode, var, n, o, p));
         for (int k = 0; k < NO; ++k)
             if (outs[k] && !dev_out[k]) FZCHK(copy_out(c, (char*)outs[k] + (size_t)i0 * row, dst[k], (size_t)n * row));
-    }
+        return 0;
+    }));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1129,15 +1161,10 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
         prev_i0 = -1;
         return 0;
     };
-    int64_t kchunk = 0;
-    for (int64_t i0 = 0; i0 < N; i0 += nc, ++kchunk) {
-        const int64_t n = std::min(nc, N - i0);
+    int64_t nchunk = 0;
+    FZCHK(for_chunks(c, x, xe, xm, N, nc, o, pb, [&](int64_t i0, int64_t n, int var, int) -> int {
+        const int64_t kchunk = nchunk++;
         const int bsel = pipe ? (int)(kchunk & 1) : 0;
-        ObjChunk ch; int fl = 0;
-        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
-        FZCHK(prior_chunk(c, pb, i0, n, M));
-        const int var = pick_var(c, fl);
-        const bool masked = var != VAR_FAST;
         double* d_pdf; double* d_lm; double* d_le;
         if (pdf_dev) d_pdf = pdfs + i0 * G;
         else {
@@ -1152,24 +1179,15 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             if (!lmap) { FZCHK(c->d_lmap.ensure((size_t)n * 8)); d_lm = c->d_lmap.as<double>(); }
             if (!levid) { FZCHK(c->d_levid.ensure((size_t)n * 8)); d_le = c->d_levid.as<double>(); }
         } else { FZCHK(lmv.at(i0, n, &d_lm)); FZCHK(lev.at(i0, n, &d_le)); }
-        if (mode == 3) {
-            c->mc_lnl_only = 1;                               // only the final ln-like plane is needed here
-            FZCHK(run_modec(c, var, n, o));
-            double* lpl = c->d_mc[1].as<double>();
-            if (!c->mc_lnl_only) FZCHK(modec_final(c, n, masked, o, lpl, nullptr, nullptr, nullptr, nullptr));   // in place: lnl plane (the one-block-per-object kernel writes it in its final form itself)
-            else c->tm.n_modec += 1;                          // (timing counters: the final pass ran inside the iteration kernel; bench.py subtracts two scopes)
-            c->mc_lnl_only = 0;
-            if (c->prior.tab) FZCHK(prior_add(c, lpl, n, M, nullptr, nullptr, nullptr, lpl));
+        if (mode == 3 || cdf) {
+            double* lpl; bool in_kernel;
+            FZCHK(chunk_lnprob_rows(c, mode, var, n, o, &lpl, &in_kernel));
+            if (in_kernel) c->tm.n_modec += 1;                // (timing counters: the final pass ran inside the iteration kernel; bench.py subtracts two scopes)
             if (cdf) {
                 FZCHK(run_cdf(c, n, (int)M, M, lpl, nullptr, nullptr, 1, ko, d_pdf, d_lm, d_le));
             } else {
                 FZCHK(fz_launch_plane_predict(c, lpl, n, M, 0, ko, d_lm, d_le, d_pdf));
             }
-        } else if (cdf) {
-            FZCHK(c->d_pl[0].ensure((size_t)n * M * 8));
-            FZCHK(run_planes(c, mode, var, o->dim_prior, n, c->d_pl[0].as<double>(), nullptr, nullptr, nullptr, nullptr));
-            if (c->prior.tab) FZCHK(prior_add(c, c->d_pl[0].as<double>(), n, M, nullptr, nullptr, nullptr, c->d_pl[0].as<double>()));
-            FZCHK(run_cdf(c, n, (int)M, M, c->d_pl[0].as<double>(), nullptr, nullptr, 1, ko, d_pdf, d_lm, d_le));
         } else {
             const int r = fitpredict_special_forms(c, mode, var, o->dim_prior, n, ko, d_lm, d_le, d_pdf);
             if (r < 0) return r;
@@ -1179,11 +1197,12 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             HIPCHK(hipEventRecord(c->ev_done[bsel], c->stream));          // chunk k is queued ...
             FZCHK(ship_prev());                                            // ... chunk k-1 leaves while it runs
             prev_i0 = i0; prev_n = n; prev_b = bsel;
-            continue;
+            return 0;
         }
         if (!pdf_dev) FZCHK(copy_out(c, pdfs + i0 * G, d_pdf, (size_t)n * G * 8));
         FZCHK(lmv.back(i0, n)); FZCHK(lev.back(i0, n));
-    }
+        return 0;
+    }));
     if (pipe) {
         FZCHK(ship_prev());
         HIPCHK(hipStreamSynchronize(c->stream));

@@ -87,7 +87,6 @@ struct fz_ctx {
     int64_t M = 0, Mp = 0; int B = 0, BT = 0;
     bool models_masked = false, models_real_masked = false, models_wild = false, models_err_const = false, models_big = false;
     int64_t mc_info[4] = {0, 0, 0, 0};   // fz_modec_info: ambiguous objects re-run, slowest object's iterations, path, block shape
-    int mc_lnl_only = 0;           // mode C: the caller of run_modec wants the final ln-like plane only (request); set back to 0 by whoever cannot honour it
     double grid_step = 0.0;        // gauss_kde grid labels: spacing of an evenly spaced grid (checked on upload), else 0
     DevBuf d_y, d_ye2, d_ye, d_mbits, d_lgA, d_lgB, d_rec0, d_rec1, d_ye2c;
     // kde dictionary (PDFDict)
@@ -270,7 +269,8 @@ struct fz_bt_table {
                   double* serr);
     int (*fitpredict)(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const fz_kde_opts* ko, double* lmap, double* levid,
                       double* pdfs);
-    int (*modec)(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr, const int64_t* nnb, int W);
+    // lnl_final: nullptr, or in: only the final ln-like plane is wanted (in d_mc[1]) / out: the kernel wrote it in its final form
+    int (*modec)(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr, const int64_t* nnb, int W, bool* lnl_final);
     int (*knnsubset)(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const int64_t* idx, int W, const fz_kde_opts* ko,
                      const fz::KnnOut* out, int* errflag);
     int (*knnquery)(fz_ctx* c, const double* q, int64_t n, int k, double bound2, int64_t* idx, int pnorm);

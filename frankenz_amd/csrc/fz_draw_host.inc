@@ -1,5 +1,5 @@
 // Host side of the posterior draws (fz_draw.h; docs/draws.md): fz_draw_logwt, fz_fit_draw, fz_knn_search_fit_draw.
-// Included by frankenz_hip.hip after the entry points it builds on (prep_chunk, prior_*, run_planes, run_modec, the k-NN calls).
+// Included by frankenz_hip.hip after the entry points it builds on (for_chunks, chunk_lnprob_rows, prior_*, the k-NN calls).
 
 static int draw_limits(const char* who, int64_t L, int64_t S) {
     if (S < 1) return fail(-4, "%s: Nsamples = %lld, need at least 1", who, (long long)S);
@@ -85,8 +85,8 @@ extern "C" int fz_draw_logwt(fz_ctx* c, const double* logwt, int64_t N, int64_t 
     return 0;
 }
 
-// objects -> draws with the built-in likelihood: the materialised route of fit_predict_impl's CDF rule (planes, or mode C's final
-// ln-like plane; + the ln-prior), chunked from the workspace limit in the same way, with the draw kernel as the rows' consumer
+// objects -> draws with the built-in likelihood: the ln-prob rows of fit_predict_impl's CDF rule (chunk_lnprob_rows), chunked from the
+// workspace limit in the same way, with the draw kernel as the rows' consumer
 extern "C" int fz_fit_draw(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, const fz_prior_lerp* pr,
                            const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
                            double* levid) {
@@ -104,27 +104,11 @@ extern "C" int fz_fit_draw(fz_ctx* c, double* x, double* xe, double* xm, int64_t
     int64_t nc = std::min<int64_t>(N, fz_dbg_int("FZ_CHUNK", 1 << 20));
     const int64_t per_obj = M * 8 * (mode == 3 ? 4 : 1) + pb.chunk_bytes_per_obj + da.staged_bytes_per_obj();
     nc = std::min<int64_t>(nc, std::max<int64_t>(1, c->ws_limit / per_obj));
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        ObjChunk ch; int fl = 0;
-        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
-        FZCHK(prior_chunk(c, pb, i0, n, M));
-        const int var = pick_var(c, fl);
-        double* lpl;
-        if (mode == 3) {
-            c->mc_lnl_only = 1;
-            FZCHK(run_modec(c, var, n, o));
-            lpl = c->d_mc[1].as<double>();
-            if (!c->mc_lnl_only) FZCHK(modec_final(c, n, var != VAR_FAST, o, lpl, nullptr, nullptr, nullptr, nullptr));
-            c->mc_lnl_only = 0;
-        } else {
-            FZCHK(c->d_pl[0].ensure((size_t)n * M * 8));
-            lpl = c->d_pl[0].as<double>();
-            FZCHK(run_planes(c, mode, var, o->dim_prior, n, lpl, nullptr, nullptr, nullptr, nullptr));
-        }
-        if (c->prior.tab) FZCHK(prior_add(c, lpl, n, M, nullptr, nullptr, nullptr, lpl));
-        FZCHK(da.run(c, i0, n, M, lpl, nullptr, nullptr, key0, key1, first, S));
-    }
+    FZCHK(for_chunks(c, x, xe, xm, N, nc, o, pb, [&](int64_t i0, int64_t n, int var, int) -> int {
+        double* lpl; bool in_kernel;
+        FZCHK(chunk_lnprob_rows(c, mode, var, n, o, &lpl, &in_kernel));
+        return da.run(c, i0, n, M, lpl, nullptr, nullptr, key0, key1, first, S);
+    }));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -146,24 +130,16 @@ extern "C" int fz_knn_search_fit_draw(fz_ctx* c, const double* q, double* x, dou
     HIPCHK(hipSetDevice(c->device));
     const bool has_prior = pr && pr->table;
     const DrawArgs da(c, u, S, idx, lmap, levid);
-    const int64_t nc = std::min<int64_t>(N, std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (W * 48 + da.staged_bytes_per_obj()), 1 << 17)));
+    const int64_t nc = std::min<int64_t>(N, std::max<int64_t>(1, std::min<int64_t>(c->ws_limit / (W * 48 + da.staged_bytes_per_obj()), knn_search_chunk_cap())));
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         FZCHK(c->d_draw[0].ensure((size_t)n * W * 8)); FZCHK(c->d_draw[1].ensure((size_t)n * 8)); FZCHK(c->d_draw[2].ensure((size_t)n * W * 8));
         if (has_prior) FZCHK(c->d_draw[3].ensure((size_t)n * W * 8));
         int64_t* d_nb = c->d_draw[0].as<int64_t>(); int64_t* d_nn = c->d_draw[1].as<int64_t>();
         double* d_lnl = c->d_draw[2].as<double>(); double* d_lpr = has_prior ? c->d_draw[3].as<double>() : nullptr;
-        fz_prior_lerp pc; const fz_prior_lerp* prc = nullptr;
-        if (has_prior) {
-            pc = *pr; prc = &pc;
-            if (pr->frac) pc.frac = pr->frac + i0;
-            if (pr->rows) pc.rows = pr->rows + i0;
-            else if (pr->P != 1) {
-                if (pr->P != N) return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
-                pc.table = pr->table + i0 * M; pc.P = n;
-            }
-        }
-        FZCHK(fz_knn_search_fit_predict_prior_lerp(c, q + i0 * F, x + i0 * B, xe + i0 * B, xm + i0 * B, n, k, lp_norm, dub, o, nullptr, prc, d_nb,
+        fz_prior_lerp pc;
+        if (has_prior) FZCHK(prior_slice(pr, i0, n, N, M, &pc));
+        FZCHK(fz_knn_search_fit_predict_prior_lerp(c, q + i0 * F, x + i0 * B, xe + i0 * B, xm + i0 * B, n, k, lp_norm, dub, o, nullptr, has_prior ? &pc : nullptr, d_nb,
                                                    d_nn, nullptr, d_lnl, d_lpr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
         FZCHK(da.run(c, i0, n, W, has_prior ? d_lpr : d_lnl, d_nb, d_nn, key0, key1, first, S));
         if (neighbors) FZCHK(copy_out(c, neighbors + i0 * W, d_nb, (size_t)n * W * 8));

@@ -148,7 +148,7 @@ static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t
 // mode C driver on a prepared chunk: leaves converged state in c->d_mc[*]
 // ---------------------------------------------------------------------------
 template <int BT, bool MASKED>
-static int run_modec(fz_ctx* c, int64_t n, const fz_like_opts* o, const SubsetView& sub, bool tame) {
+static int run_modec(fz_ctx* c, int64_t n, const fz_like_opts* o, const SubsetView& sub, bool tame, bool* lnl_final) {
     const int64_t M = sub.nbr ? sub.W : c->M;
     const size_t pl = (size_t)n * M * 8;
     for (int k = 0; k < 4; ++k) FZCHK(c->d_mc[k].ensure(pl));
@@ -179,8 +179,8 @@ static int run_modec(fz_ctx* c, int64_t n, const fz_like_opts* o, const SubsetVi
     const int max_iter = o->max_iter > 0 ? o->max_iter : 10000;
     const int burst = std::max(1, (int)fz_dbg_int("FZ_MODEC_BURST", 8));
     Timer t(c, &c->tm.ms_modec, &c->tm.n_modec);
-    const int want_lnl_only = c->mc_lnl_only;
-    c->mc_lnl_only = 0;                                  // honoured below by the one-block-per-object path only (and not for neighbour subsets)
+    const bool want_lnl_only = lnl_final && *lnl_final;
+    if (lnl_final) *lnl_final = false;                   // honoured below by the one-block-per-object path only (and not for neighbour subsets)
     // counters of the device, read back (waits for the stream)
     auto read_back = [&](int* dst, const int* src, int nwords) -> int {
         HIPCHK(hipMemcpyAsync(dst, src, 4 * nwords, hipMemcpyDeviceToHost, c->stream));
@@ -237,7 +237,7 @@ static int run_modec(fz_ctx* c, int64_t n, const fz_like_opts* o, const SubsetVi
     const bool rounds = fz_dbg_str("FZ_MODEC_ROUNDS")[0] != '0';
     const bool wide = M > FZ_MCP_MAXM;
     if (!fz_dbg_set("FZ_MODEC_PLANES") && (wide ? fast && rounds : true)) {
-        if (!wide && want_lnl_only && !sub.nbr && !fz_dbg_set("FZ_MODEC_FINAL")) { st.lnl_only = o->dim_prior ? 2 : 1; c->mc_lnl_only = 1; }
+        if (!wide && want_lnl_only && !sub.nbr && !fz_dbg_set("FZ_MODEC_FINAL")) { st.lnl_only = o->dim_prior ? 2 : 1; *lnl_final = true; }
         // the persistent launch of every shape: as many blocks as stay resident, objects handed out through the queue head counts[4]
         auto launch = [&](auto kern, int T, size_t lds, const int* list, int64_t nobj) -> int {
             int64_t blocks = 0;
@@ -311,13 +311,13 @@ static int run_modec(fz_ctx* c, int64_t n, const fz_like_opts* o, const SubsetVi
     return 0;
 }
 
-static int fz_modec_bt(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr, const int64_t* nnb, int W) {
+static int fz_modec_bt(fz_ctx* c, int var, int64_t n, const fz_like_opts* o, const int64_t* nbr, const int64_t* nnb, int W, bool* lnl_final) {
     SubsetView sub; sub.nbr = nbr; sub.nnb = nnb; sub.W = W;
 #if FZ_EXACT_BT
-    return var == VAR_FAST ? run_modec<FZ_BT, false>(c, n, o, sub, true) : run_modec<FZ_BT, true>(c, n, o, sub, false);
+    return var == VAR_FAST ? run_modec<FZ_BT, false>(c, n, o, sub, true, lnl_final) : run_modec<FZ_BT, true>(c, n, o, sub, false, lnl_final);
 #else
     (void)var;
-    return run_modec<FZ_BT, true>(c, n, o, sub, false);
+    return run_modec<FZ_BT, true>(c, n, o, sub, false, lnl_final);
 #endif
 }
 

@@ -141,6 +141,13 @@ static int check_knn_k(const fz_ctx* c, int k, int pnorm, const char* who) {
         return fail(-5, "%s: k=%d > 64 needs the Euclidean norm and at most 6 features (the other searches keep one list entry per lane)", who, k);
     return 0;
 }
+// the norm and bound of a search as the kernels take them: pnorm 2 / 1 / 0 (inf), b2 the bound (squared under the Euclidean norm)
+static int parse_lp_norm(const char* who, double lp_norm, double dub, int* pnorm, double* b2) {
+    if (lp_norm == 2.0) *pnorm = 2; else if (lp_norm == 1.0) *pnorm = 1; else if (lp_norm == INFINITY) *pnorm = 0;
+    else return fail(-5, "%s: Minkowski p=%g is not implemented (1, 2 and inf are)", who, lp_norm);
+    *b2 = (dub == INFINITY || *pnorm != 2) ? dub : dub * dub;      // KDTree keeps d < bound (strict)
+    return 0;
+}
 static int run_knnquery(fz_ctx* c, const double* q, int64_t n, int k, double b2, int64_t* idx, int pnorm) {
     if (knn_on_matrix_pipe(c, pnorm)) {
         // register lists (row-parallel admissions) for k <= 32, the reference's default is 20; FZ_KNN_SERIAL=1: the wave-serial LDS lists
@@ -224,11 +231,9 @@ extern "C" int fz_knn_query(fz_ctx* c, const double* q, int64_t N, int32_t k, do
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {q, idx}));
     const int F = c->knn_F, K = c->knn_K;
-    int pnorm;
-    if (lp_norm == 2.0) pnorm = 2; else if (lp_norm == 1.0) pnorm = 1; else if (lp_norm == INFINITY) pnorm = 0;
-    else return fail(-5, "fz_knn_query: Minkowski p=%g is not implemented (1, 2 and inf are)", lp_norm);
+    int pnorm; double b2;
+    FZCHK(parse_lp_norm("fz_knn_query", lp_norm, dub, &pnorm, &b2));
     FZCHK(check_knn_k(c, k, pnorm, "fz_knn_query"));
-    const double b2 = (dub == INFINITY || pnorm != 2) ? dub : dub * dub;      // KDTree keeps d < bound (strict)
     const StageRows qv(c, q, (size_t)F * 8, c->d_q, STAGE_IN), iv(c, idx, (size_t)K * k * 8, c->d_idx, STAGE_OUT);
     const int64_t nc = std::min<int64_t>(N, 1 << 18);
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
@@ -288,12 +293,7 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
     // iterative likelihood, CDF rule and priors work from materialised (n,W) rows; the plain
     // case is one fused kernel
     const bool rows_route = (mode == 3) || cdf || want_prior;
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        ObjChunk ch; int fl = 0;
-        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
-        FZCHK(prior_chunk(c, pb, i0, n, c->M));
-        const int var = pick_var(c, fl);
+    FZCHK(for_chunks(c, x, xe, xm, N, nc, o, pb, [&](int64_t i0, int64_t n, int var, int) -> int {
         const int64_t* di;
         FZCHK(iv.at(i0, n, &di));
         void* dev[NO];
@@ -323,7 +323,7 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
                     return 0;
                 }));
                 if (!ef) {
-                    FZCHK(run_modec(c, var, n, o, nb, nn, (int)W));
+                    FZCHK(run_modec(c, var, n, o, nullptr, nb, nn, (int)W));
                     if (!lpl) lpl = c->d_mc[1].as<double>();                     // in place on the state plane
                     FZCHK(modec_final(c, n, var != VAR_FAST, o, lpl, ko_.chi2, ko_.ndim, ko_.scale, ko_.serr, nb, nn, (int)W));
                 }
@@ -354,7 +354,8 @@ extern "C" int fz_knn_fit_predict_prior_lerp(fz_ctx* c, double* x, double* xe, d
         if (ef) return fail(-3, "a neighbour index is outside [0, Nmodel): KDTree returns Nmodel for neighbours beyond "
                                 "distance_upper_bound and the reference then fails on models[idxs] (knn.py:847)");
         for (auto& u : outs) FZCHK(u.back(i0, n));
-    }
+        return 0;
+    }));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -366,10 +367,23 @@ extern "C" int fz_knn_fit_predict(fz_ctx* c, double* x, double* xe, double* xm, 
                                          scale, scale_err, pdfs, lmap, levid);
 }
 
+// objects per chunk of the two search drivers (fz_knn_search_fit_predict*, fz_knn_search_fit_draw) at the most
+static int64_t knn_search_chunk_cap() { return std::max<int64_t>(1, std::min<int64_t>(1 << 17, fz_dbg_int("FZ_CHUNK", 1 << 17))); }
+// *out: the prior of objects [i0, i0 + n) of N, for a driver that hands its chunks to another entry point
+static int prior_slice(const fz_prior_lerp* pr, int64_t i0, int64_t n, int64_t N, int64_t M, fz_prior_lerp* out) {
+    *out = *pr;
+    if (pr->frac) out->frac = pr->frac + i0;
+    if (pr->rows) out->rows = pr->rows + i0;
+    else if (pr->P != 1) {
+        if (pr->P != N) return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
+        out->table = pr->table + i0 * M; out->P = n;
+    }
+    return 0;
+}
 // knn.py:826-874 in one call: the K searches AND the subset likelihood / PDFs, with the (N, K*k) neighbour table never leaving the
 // device (it is 4 GB at 1e6 objects x 500 and the two-call form above bounced it through the host: 4 GB out of fz_knn_query,
 // 4 GB into fz_knn_fit_predict).  q (N,F): the query features (knn.py:830-832; the caller draws them, so the stream is the
-// reference's).  Searched and fitted in chunks of <= 2^17 objects.
+// reference's).  Searched and fitted in chunks of <= 2^17 objects (FZ_CHUNK: fewer).
 extern "C" int fz_knn_search_fit_predict_prior(fz_ctx* c, const double* q, double* x, double* xe, double* xm, int64_t N, int32_t k,
                                                double lp_norm, double dub, const fz_like_opts* o, const fz_kde_opts* ko,
                                                const fz_prior* pr, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike,
@@ -394,31 +408,21 @@ extern "C" int fz_knn_search_fit_predict_prior_lerp(fz_ctx* c, const double* q, 
     FZCHK(wait_for_producers(c, {q, x, xe, xm}));
     const int F = c->knn_F, K = c->knn_K, B = c->B;
     const int64_t W = (int64_t)K * k, G = c->G, M = c->M;
-    int pnorm;
-    if (lp_norm == 2.0) pnorm = 2; else if (lp_norm == 1.0) pnorm = 1; else if (lp_norm == INFINITY) pnorm = 0;
-    else return fail(-5, "fz_knn_search_fit_predict: Minkowski p=%g is not implemented (1, 2 and inf are)", lp_norm);
+    int pnorm; double b2;
+    FZCHK(parse_lp_norm("fz_knn_search_fit_predict", lp_norm, dub, &pnorm, &b2));
     FZCHK(check_knn_k(c, k, pnorm, "fz_knn_search_fit_predict"));
-    const double b2 = (dub == INFINITY || pnorm != 2) ? dub : dub * dub;
     const StageRows qv(c, q, (size_t)F * 8, c->d_q, STAGE_IN);
-    const int64_t nc = std::min<int64_t>(N, 1 << 17);
+    const int64_t nc = std::min<int64_t>(N, knn_search_chunk_cap());
     FZCHK(c->d_idxs.ensure((size_t)nc * W * 8));
     for (int64_t i0 = 0; i0 < N; i0 += nc) {
         const int64_t n = std::min(nc, N - i0);
         const double* dq;
         FZCHK(qv.at(i0, n, &dq));
         FZCHK(run_knnquery(c, dq, n, k, b2, c->d_idxs.as<int64_t>(), pnorm));
-        fz_prior_lerp pc; const fz_prior_lerp* prc = nullptr;
-        if (pr && pr->table) {
-            pc = *pr; prc = &pc;
-            if (pr->frac) pc.frac = pr->frac + i0;
-            if (pr->rows) pc.rows = pr->rows + i0;
-            else if (pr->P != 1) {
-                if (pr->P != N) return fail(-4, "ln-prior table has %lld rows for %lld objects and no row index", (long long)pr->P, (long long)N);
-                pc.table = pr->table + i0 * M; pc.P = n;
-            }
-        }
+        fz_prior_lerp pc; const bool has_prior = pr && pr->table;
+        if (has_prior) FZCHK(prior_slice(pr, i0, n, N, M, &pc));
         auto at = [&](auto* p, int64_t per) { return p ? p + i0 * per : p; };
-        FZCHK(fz_knn_fit_predict_prior_lerp(c, x + i0 * B, xe + i0 * B, xm + i0 * B, n, c->d_idxs.as<int64_t>(), W, o, ko, prc, at(neighbors, W),
+        FZCHK(fz_knn_fit_predict_prior_lerp(c, x + i0 * B, xe + i0 * B, xm + i0 * B, n, c->d_idxs.as<int64_t>(), W, o, ko, has_prior ? &pc : nullptr, at(neighbors, W),
                                             at(nnbr, 1), at(lnprior, W), at(lnlike, W), at(lnprob, W), at(chi2, W), at(ndim, W), at(scale, W),
                                             at(scale_err, W), at(pdfs, G), at(lmap, 1), at(levid, 1)));
     }

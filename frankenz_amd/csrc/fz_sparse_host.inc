@@ -1,5 +1,5 @@
 // Host side of the sparse fits (fz_sparse.h; docs/sparse_fits.md): fz_sparsify_logwt, fz_fit_sparse.
-// Included by frankenz_hip.hip after fz_draw_host.inc (prep_chunk, prior_*, run_planes, run_modec, modec_final are above).
+// Included by frankenz_hip.hip after fz_draw_host.inc (for_chunks, chunk_planes, prior_* are above).
 
 static int sparse_limits(const char* who, int64_t L, int64_t W, double lncut) {
     if (W < 1) return fail(-4, "%s: Nkeep = %lld, need at least 1", who, (long long)W);
@@ -91,8 +91,8 @@ extern "C" int fz_sparsify_logwt(fz_ctx* c, const double* logwt, int64_t N, int6
     return 0;
 }
 
-// objects -> sparse rows with the built-in likelihood: the materialised route of fz_fit_draw with the planes asked for, the selection
-// on the ln-prob plane and one gather per other plane
+// objects -> sparse rows with the built-in likelihood: fz_fit's planes (chunk_planes) as far as asked for, the selection on the
+// ln-prob plane and one gather per other plane
 extern "C" int fz_fit_sparse(fz_ctx* c, double* x, double* xe, double* xm, int64_t N, const fz_like_opts* o, const fz_prior_lerp* pr, int64_t W,
                              double lncut, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
                              int64_t* ndim, double* scale, double* scale_err, double* lmap, double* levid, double* lnkept) {
@@ -121,33 +121,21 @@ extern "C" int fz_fit_sparse(fz_ctx* c, double* x, double* xe, double* xm, int64
     int64_t nc = std::min<int64_t>(N, fz_dbg_int("FZ_CHUNK", 1 << 18));
     nc = std::min<int64_t>(nc, std::max<int64_t>(1, c->ws_limit / per_obj));
     const uint64_t ninf = bits_of(-INFINITY), pinf = bits_of(INFINITY), one = bits_of(1.0), zero = bits_of(0.0);
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        ObjChunk ch; int fl = 0;
-        FZCHK(prep_chunk(c, x, xe, xm, i0, n, obj_vmode(c, like_mode(o)), true, ch, fl));
-        FZCHK(prior_chunk(c, pb, i0, n, M));
-        const int var = pick_var(c, fl);
-        const size_t pbytes = (size_t)n * M * 8;
-        FZCHK(c->d_pl[0].ensure(pbytes));
-        double* p_lnl = c->d_pl[0].as<double>();
-        double *p_chi2 = nullptr, *p_sc = nullptr, *p_se = nullptr, *p_lpr = nullptr, *p_lpb = p_lnl; int64_t* p_nd = nullptr;
-        if (chi2) { FZCHK(c->d_pl[1].ensure(pbytes)); p_chi2 = c->d_pl[1].as<double>(); }
-        if (ndim) { FZCHK(c->d_pl[2].ensure(pbytes)); p_nd = c->d_pl[2].as<int64_t>(); }
-        if (scale) { FZCHK(c->d_pl[3].ensure(pbytes)); p_sc = c->d_pl[3].as<double>(); }
-        if (scale_err) { FZCHK(c->d_pl[4].ensure(pbytes)); p_se = c->d_pl[4].as<double>(); }
-        if (has_prior && lnprior) { FZCHK(c->d_pl[5].ensure(pbytes)); p_lpr = c->d_pl[5].as<double>(); }
-        if (own_lnprob) { FZCHK(c->d_pl[6].ensure(pbytes)); p_lpb = c->d_pl[6].as<double>(); }
-        if (mode == 3) {
-            FZCHK(run_modec(c, var, n, o));
-            FZCHK(modec_final(c, n, var != VAR_FAST, o, p_lnl, p_chi2, p_nd, p_sc, p_se));
-        } else {
-            FZCHK(run_planes(c, mode, var, o->dim_prior, n, p_lnl, p_chi2, p_nd, p_sc, p_se));
+    FZCHK(for_chunks(c, x, xe, xm, N, nc, o, pb, [&](int64_t i0, int64_t n, int var, int) -> int {
+        const bool want[7] = {true, chi2 != nullptr, ndim != nullptr, scale != nullptr, scale_err != nullptr, has_prior && lnprior, own_lnprob};
+        void* pl[7];
+        for (int k = 0; k < 7; ++k) {
+            if (want[k]) FZCHK(c->d_pl[k].ensure((size_t)n * M * 8));
+            pl[k] = want[k] ? c->d_pl[k].p : nullptr;
         }
-        if (has_prior) FZCHK(prior_add(c, p_lnl, n, M, nullptr, nullptr, p_lpr, p_lpb));
+        Planes p; p.lnl = (double*)pl[0]; p.chi2 = (double*)pl[1]; p.ndim = (int64_t*)pl[2]; p.scale = (double*)pl[3];
+        p.serr = (double*)pl[4]; p.lnprior = (double*)pl[5];
+        if (has_prior) p.lnprob = own_lnprob ? (double*)pl[6] : p.lnl;
+        FZCHK(chunk_planes(c, mode, var, n, o, p));
         int64_t *dn, *dc;
-        FZCHK(sa.run(c, i0, n, M, p_lpb, W, lncut, &dn, &dc));
+        FZCHK(sa.run(c, i0, n, M, has_prior ? p.lnprob : p.lnl, W, lncut, &dn, &dc));
         // (without a prior the ln-prior of a kept entry is 0 and ln-prob is the ln-like: bruteforce.py:195-203 through pdf.py:404-405)
-        const void* gplanes[6] = {p_lpr, p_lnl, p_chi2, p_nd, p_sc, p_se};      // (p_lnl is intact whenever lnlike is asked for)
+        const void* gplanes[6] = {p.lnprior, p.lnl, p.chi2, p.ndim, p.scale, p.serr};      // (p.lnl is intact whenever lnlike is asked for)
         const uint64_t gpads[6] = {ninf, ninf, pinf, 0, one, zero};
         for (int k = 0; k < 6; ++k) {
             if (!gouts[k]) continue;
@@ -157,7 +145,8 @@ extern "C" int fz_fit_sparse(fz_ctx* c, double* x, double* xe, double* xm, int64
             FZCHK(run_sparse_gather(c, gplanes[k], n, M, dn, dc, W, zero, gpads[k], dg));
             FZCHK(gv.back(i0, n));
         }
-    }
+        return 0;
+    }));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -132,6 +132,32 @@ def test_fit_sample_is_fit_then_sample(which):
     gof_close((lm, le), (rlm, rle))
 
 
+@pytest.mark.parametrize('final', ['in-kernel', 'separate'])
+def test_fit_sample_mode_c_with_a_prior_table(final, monkeypatch):
+    """free scale WITH model errors (mode C at 5 bands) under a ln-prior table: the prior is added in place on the ln-like state
+    plane, which the iteration kernel finishes itself or (FZ_MODEC_FINAL=1) a separate k_modec_final pass does.  Against the oracle's
+    rows; and under FZ_CHUNK=16 (three chunks) the call returns the same bits."""
+    import frankenz_oracle as fo
+    from frankenz_amd import BruteForce
+    (X, Xe, Xm, Y, Ye, Ym, u), ptab, _, lp_tab, _ = priors_of(257, 37)
+    S = u.shape[1]
+    if final == 'separate':
+        monkeypatch.setenv('FZ_MODEC_FINAL', '1')
+    run = lambda: BruteForce(Y, Ye, Ym).fit_sample(X.copy(), Xe.copy(), Xm.copy(), S, lprob_func=ptab, lprob_kwargs={'free_scale': True},
+                                                   rstate=np.random.RandomState(5), draws='host', return_gof=True, verbose=False)
+    idx, (lm, le) = run()
+    rows = fo.bruteforce_fit(X.copy(), Xe.copy(), Xm.copy(), Y, Ye, Ym, lnprior=lp_tab, free_scale=True)['lnprob']
+    uu = np.random.RandomState(5).rand(*u.shape)
+    close = dr.near(rows, uu, dr.FIT_TOL)
+    assert close.mean() <= dr.NEAR_CAP
+    ref, rlm, rle = dr.draw_ref(rows, uu)
+    dr.assert_draws(idx, ref, rows, close)
+    gof_close((lm, le), (rlm, rle))
+    monkeypatch.setenv('FZ_CHUNK', '16')
+    idx2, (lm2, le2) = run()
+    np.testing.assert_array_equal(idx2, idx); np.testing.assert_array_equal(lm2, lm); np.testing.assert_array_equal(le2, le)
+
+
 def test_device_draws_are_philox_at_object_and_draw():
     from frankenz_amd import BruteForce
     from frankenz_amd.samplers import _philox_uniform

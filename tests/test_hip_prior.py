@@ -182,6 +182,39 @@ def test_g9_knn_prior_hook_golden(tag, kw):
     close(p2, g[tag + '_pdfs'], rtol=1e-8, atol=1e-13)
 
 
+@pytest.mark.parametrize('form', ['dense', 'rows', 'lerp'])
+def test_knn_search_chunks_take_their_slice_of_the_prior(form, monkeypatch):
+    """FZ_CHUNK=16 splits the 37 objects of the two search drivers (fit_predict, fit_sample) into three chunks, each handed on with
+    its slice of the prior -- rows of a dense (N, M) table, row indices, interpolation weights: bit for bit the unchunked call"""
+    import _draw_ref as dr
+    from frankenz_amd import NearestNeighbors
+    from frankenz_amd.pdf import logprob_prior, logprob_prior_lerp
+    X, Xe, Xm, Y, Ye, Ym, S = dr.knn_problem(3, 4)
+    N, M = len(X), len(Y)
+    rs = np.random.RandomState(66)
+    z, ze = rs.uniform(0, 6, M), rs.uniform(0.02, 0.1, M)
+    if form == 'dense':
+        hook = logprob_prior(rs.normal(0., 2., size=(N, M)))
+    elif form == 'rows':
+        hook = logprob_prior(rs.normal(0., 2., size=(7, M)), rs.randint(0, 7, N))
+    else:
+        hook = logprob_prior_lerp(rs.uniform(0.05, 1., size=(6, M)), np.linspace(18., 23., 6), rs.uniform(17.5, 23.5, N))
+    d, _ = dicts()
+
+    def run():
+        nn = NearestNeighbors(Y, Ye, Ym, K=3, rstate=np.random.RandomState(1), verbose=False)
+        p, (lm, le) = nn.fit_predict(X.copy(), Xe.copy(), Xm.copy(), z, ze, lprob_func=hook, rstate=np.random.RandomState(2), k=4,
+                                     label_dict=d, return_gof=True, verbose=False)
+        idx = nn.fit_sample(X.copy(), Xe.copy(), Xm.copy(), S, lprob_func=hook, rstate=np.random.RandomState(3), k=4, verbose=False)
+        assert np.isfinite(p).all() and (idx >= 0).all()
+        return p, lm, le, idx
+
+    base = run()
+    monkeypatch.setenv('FZ_CHUNK', '16')
+    for a, b in zip(run(), base):
+        np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize('kw,kk', [({'free_scale': True}, {}), ({}, {'wt_thresh': None, 'cdf_thresh': 0.02})])
 def test_knn_prior_other_routes_vs_oracle(kw, kk):
     from frankenz_amd import NearestNeighbors

@@ -197,12 +197,13 @@ def fitted(tag):
         return X, Xe, Xm, Y, Ye, Ym, None, {}, False, fo.bruteforce_fit(X.copy(), Xe.copy(), Xm.copy(), Y, Ye, Ym)
     if tag.startswith('prior'):
         X, Xe, Xm, Y, Ye, Ym, tab, prow, vals, grid, coord, _ = dr.prior_problem()
-        if tag == 'prior-table':
+        kw = {'free_scale': True} if tag.endswith('-C') else {}
+        if tag.startswith('prior-table'):
             func, lp = pdf.logprob_prior(tab, rows=prow), tab[prow]
         else:
             r, f = lerp_cells(grid, coord)
             func, lp = pdf.logprob_prior_lerp(vals, grid, coord), np.log((1 - f)[:, None] * vals[r] + f[:, None] * vals[r + 1])
-        return X, Xe, Xm, Y, Ye, Ym, func, {}, False, fo.bruteforce_fit(X.copy(), Xe.copy(), Xm.copy(), Y, Ye, Ym, lnprior=lp)
+        return X, Xe, Xm, Y, Ye, Ym, func, kw, False, fo.bruteforce_fit(X.copy(), Xe.copy(), Xm.copy(), Y, Ye, Ym, lnprior=lp, **kw)
     if tag == 'scaleB':
         p = dr.fit_problem(dr.FIT_CASES[1])
         kw = dict(p['kw'], return_scale=True)
@@ -213,9 +214,10 @@ def fitted(tag):
 
 
 @pytest.mark.parametrize('tag', ['fit0', 'fit1', 'fit2', 'fit3', 'fit4', 'fit5', 'masked5', 'masked12', 'masked32', 'prior-table', 'prior-lerp',
-                                 'scaleB'])
+                                 'prior-table-C', 'scaleB'])
 def test_fit_sparse_is_the_law_on_the_planes(tag):
-    """fit0..5: _draw_ref.FIT_CASES (modes A, B, dim_prior=False, W > Nmodel, 70 001 models, and mode C at 12 bands: fit5)"""
+    """fit0..5: _draw_ref.FIT_CASES (modes A, B, dim_prior=False, W > Nmodel, 70 001 models, and mode C at 12 bands: fit5);
+    prior-table-C: the table prior under mode C at 5 bands"""
     from frankenz_amd import BruteForce
     X, Xe, Xm, Y, Ye, Ym, func, kw, track, oracle = fitted(tag)
     N, M = len(X), len(Y)
