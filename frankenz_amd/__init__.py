@@ -13,9 +13,9 @@ from .bruteforce import BruteForce
 from .knn import NearestNeighbors
 from .samplers import model_weight_em, model_weight_sampler
 from .sparse import SparseFits
-from . import fitting, networks, pdf, plotting, priors, reddening, samplers, simulate
+from . import calibrate, fitting, networks, pdf, plotting, priors, reddening, samplers, simulate
 
 __version__ = "0.1.0"
 __all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gauss_kde",
            "gauss_kde_dict", "loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "luptitude", "magnitude",
-           "pdfs_resample", "pdfs_summarize", "sample_labels", "model_weight_sampler", "model_weight_em", "SparseFits", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]
+           "pdfs_resample", "pdfs_summarize", "sample_labels", "model_weight_sampler", "model_weight_em", "SparseFits", "calibrate", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]

@@ -510,6 +510,31 @@ class BruteForce():
             raise ValueError("Fits have not been computed.")
         return model_weight_em(self.fit_lnlike, device=self._device)
 
+    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
+        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
+        posterior mean redshift without a grid -- under the stored dense ``fit_lnprob`` rows or the given ``(Ndata, Nmodel)`` rows
+        (``pdf.posterior_moments``).  ``use_scale`` multiplies each model's values by its fitted ``fit_scale``."""
+        from .pdf import posterior_moments
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        if use_scale and self.fit_scale is None:
+            raise ValueError("Fits have not been computed: no scales to use.")
+        return posterior_moments(logwt, values, value_errs, value_mask, scale=self.fit_scale if use_scale else None, device=self._device)
+
+    def predict_phot(self, logwt=None):
+        """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
+        mean and variance of ``scale * model flux`` per band under the stored fits, the model errors added as the law of total
+        variance, masked model bands left out per band (``share``: the weight that was not)."""
+        from .pdf import posterior_moments
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        return posterior_moments(logwt, self.models, self.models_err, self.models_mask, scale=self.fit_scale, return_share=True,
+                                 device=self._device)
+
     def fit_sparse(self, data, data_err, data_mask, Nkeep=256, wt_thresh=1e-3, lprob_func=None, lprob_args=None, lprob_kwargs=None,
                    track_scale=False, resident=False, verbose=True):
         """Extension (no reference counterpart; docs/sparse_fits.md): one exhaustive fit that leaves, per object, the exact ``Nkeep``

@@ -144,6 +144,8 @@ struct fz_ctx {
     DevBuf d_mwem[12];
     // sparse fits (fz_sparse_host.inc): lnkept, the kept ln-prob rows, the gathered rows of one plane at a time
     DevBuf d_sparse[3];
+    // posterior moments and zero-point sums (fz_moments_host.inc, which lists them)
+    DevBuf d_mom[9];
 
     std::vector<DevBuf*> all_bufs() {
         std::vector<DevBuf*> v = {&d_y, &d_ye2, &d_ye, &d_rec0, &d_rec1, &d_ye2c, &d_mbits, &d_lgA, &d_lgB, &d_widths, &d_offsets, &d_kern, &d_pos,
@@ -157,6 +159,7 @@ struct fz_ctx {
         for (auto& b : d_mw) v.push_back(&b);
         for (auto& b : d_mwem) v.push_back(&b);
         for (auto& b : d_sparse) v.push_back(&b);
+        for (auto& b : d_mom) v.push_back(&b);
         return v;
     }
 };

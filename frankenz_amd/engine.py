@@ -399,6 +399,23 @@ class Engine(object):
         check(self.lib.fz_mw_em(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(co), ptr(cj), ptr(cv), int(entries),
                                 ptr(alpha), ptr(lnw), int(niter), ptr(pos), ptr(counts), ptr(trace), ptr(nskip)))
 
+    # -- posterior moments and zero-point sums (docs/predictive.md; fz_moments.h) ----
+    def row_moments(self, rows, n, W, M, L, values, mean, var=None, share=None, value_errs=None, value_mask=None, scale=None,
+                    neighbors=None, nnbr=None):
+        """fz_row_moments: rows (n, W) of ln-weights over ``values`` (M, L) -> ``mean`` (n, L) [, ``var``, ``share``]; returns the
+        number of rows without a posterior"""
+        ns = np.zeros(1, dtype=np.int64)
+        check(self.lib.fz_row_moments(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), ptr(scale), int(M), int(L), ptr(values),
+                                      ptr(value_errs), ptr(value_mask), ptr(mean), ptr(var), ptr(share), ptr(ns)))
+        return int(ns[0])
+
+    def phot_sums(self, x, xe, xm, mean, var, n, B, clip=0.):
+        """fz_phot_sums -> (sums (3, B) float64 = A, B, C; counts (2, B) int64 = n, nclip)"""
+        sums, counts = np.zeros((3, int(B))), np.zeros((2, int(B)), dtype=np.int64)
+        check(self.lib.fz_phot_sums(self.h, ptr(x), ptr(xe), ptr(xm), ptr(mean), ptr(var), int(n), int(B), float(clip), ptr(sums),
+                                    ptr(counts)))
+        return sums, counts
+
     # -- k-NN ------------------------------------------------------------
     def knn_upload_trees(self, feats, key=None):
         """``key``: the caller's content key of ``feats`` (``_digest``); an unchanged set is not sent (nor Morton-sorted) again"""

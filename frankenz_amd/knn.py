@@ -632,6 +632,31 @@ class NearestNeighbors():
         return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
                                device=self._device)
 
+    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
+        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
+        posterior mean redshift without a grid -- under the stored fits (``fit_lnprob`` beside ``neighbors`` / ``Nneighbors``) or the
+        given padded ``(Ndata, K*k)`` rows (``pdf.posterior_moments``).  ``use_scale`` multiplies each entry's values by its
+        fitted ``fit_scale``."""
+        from .pdf import posterior_moments
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None or getattr(self, "neighbors", None) is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        return posterior_moments(logwt, values, value_errs, value_mask, scale=self.fit_scale if use_scale else None,
+                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, device=self._device)
+
+    def predict_phot(self, logwt=None):
+        """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
+        mean and variance of ``scale * model flux`` per band under the stored fits, the model errors added as the law of total
+        variance, masked model bands left out per band (``share``: the weight that was not)."""
+        from .pdf import posterior_moments
+        if logwt is None:
+            logwt = self.fit_lnprob
+        if logwt is None or getattr(self, "neighbors", None) is None:
+            raise ValueError("Fits have not been computed and weights have not been provided.")
+        return posterior_moments(logwt, self.models, self.models_err, self.models_mask, scale=self.fit_scale,
+                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, return_share=True, device=self._device)
+
     # ------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None,
                 kde_args=None, kde_kwargs=None, return_gof=False, verbose=True):

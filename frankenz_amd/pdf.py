@@ -17,7 +17,7 @@ import numpy as np
 from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
-           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt"]
+           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt", "posterior_moments"]
 
 
 def _ndim_dtype(data_mask, models_mask):
@@ -238,6 +238,58 @@ def sparsify_logwt(logwt, Nkeep=256, wt_thresh=1e-3, device=None):
     if N:
         get_engine(device).sparsify_logwt(lw, W, lncut, nbr, cnt, vals=vals, lmap=lmap, levid=levid, lnkept=lnkept, n=N, M=M)
     return SparseFits(nbr, cnt, M, lmap, levid, lnkept, fit_lnprob=vals, device=device)
+
+
+def _rows_arg(a, dtype, name):
+    """a NumPy array made C-contiguous in ``dtype``, or a device array of 8-byte items used where it lies"""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        if (hasattr(a, "element_size") and a.element_size() != 8) or (hasattr(a, "is_contiguous") and not a.is_contiguous()):
+            raise ValueError("`%s` on the device must be C-contiguous with 8-byte items" % name)
+        return a
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def posterior_moments(logwt, values, value_errs=None, value_mask=None, scale=None, neighbors=None, Nneighbors=None,
+                      return_share=False, device=None):
+    """Posterior mean and variance of per-model values under rows of ln-weights (extension; docs/predictive.md states the law).
+
+    ``logwt`` ``(Ndata, W)``; with ``neighbors`` ``(Ndata, W)`` / ``Nneighbors`` ``(Ndata,)`` entry ``t`` of a row belongs to model
+    ``neighbors[i, t]`` and only the first ``Nneighbors[i]`` count, without them the rows are dense (``W == Nmodel``).  ``values``
+    ``(Nmodel, L)`` or ``(Nmodel,)`` (one column; the results are then ``(Ndata,)``), ``value_errs`` their standard deviations
+    (added as the law of total variance), ``value_mask`` non-zero where a value is usable, ``scale`` ``(Ndata, W)`` a factor per
+    entry.  Every array is NumPy or a device array.  Returns ``(mean, var)`` or ``(mean, var, share)``; ``share`` is the part of
+    the row's weight that had a usable value.  A row without a posterior gives nan (share 0)."""
+    if (neighbors is None) != (Nneighbors is None):
+        raise ValueError("`neighbors` and `Nneighbors` come together")
+    lw = _rows_arg(logwt, np.float64, "logwt")
+    V = _rows_arg(values, np.float64, "values")
+    one = len(V.shape) == 1
+    if len(lw.shape) != 2 or len(V.shape) not in (1, 2):
+        raise ValueError("`logwt` must be (Ndata, W) and `values` (Nmodel, L) or (Nmodel,)")
+    N, W = (int(v) for v in lw.shape)
+    M, L = int(V.shape[0]), (1 if one else int(V.shape[1]))
+    Ve, Vm = _rows_arg(value_errs, np.float64, "value_errs"), _rows_arg(value_mask, np.float64, "value_mask")
+    for a, name in ((Ve, "value_errs"), (Vm, "value_mask")):
+        if a is not None and tuple(a.shape) != tuple(V.shape):
+            raise ValueError("`%s` has shape %s, `values` %s" % (name, tuple(a.shape), tuple(V.shape)))
+    sc = _rows_arg(scale, np.float64, "scale")
+    nb, nn = _rows_arg(neighbors, np.int64, "neighbors"), _rows_arg(Nneighbors, np.int64, "Nneighbors")
+    if sc is not None and tuple(sc.shape) != (N, W):
+        raise ValueError("`scale` has shape %s, `logwt` %s" % (tuple(sc.shape), (N, W)))
+    if nb is not None and (tuple(nb.shape) != (N, W) or tuple(nn.shape) != (N,)):
+        raise ValueError("`neighbors` must have the shape of `logwt` and `Nneighbors` one entry per object")
+    if nb is None and W != M:
+        raise ValueError("dense rows have one entry per model: %d entries, %d models" % (W, M))
+    if W < 1 or M < 1 or L < 1:
+        raise ValueError("rows of %d entries over %d models and %d columns" % (W, M, L))
+    mean, var = np.full((N, L), np.nan), np.full((N, L), np.nan)
+    share = np.zeros((N, L)) if return_share else None
+    get_engine(device).row_moments(lw, N, W, M, L, V, mean, var=var, share=share, value_errs=Ve, value_mask=Vm, scale=sc,
+                                   neighbors=nb, nnbr=nn)
+    out = (mean, var, share) if return_share else (mean, var)
+    return tuple(a[:, 0] for a in out) if one else out
 
 
 def gaussian(mu, std, x):

@@ -115,3 +115,23 @@ class SparseFits(object):
             raise ValueError("the ln-likelihood rows were not kept")
         return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
                                device=self._device)
+
+    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
+        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
+        posterior mean redshift without a grid -- from the sparse rows (``pdf.posterior_moments``).  ``use_scale`` multiplies each
+        entry's values by its fitted ``fit_scale``."""
+        from .pdf import posterior_moments
+        if use_scale and self.fit_scale is None:
+            raise ValueError("the scale rows were not kept (`track_scale=True`)")
+        return posterior_moments(self._rows(logwt), values, value_errs, value_mask, scale=self.fit_scale if use_scale else None,
+                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, device=self._device)
+
+    def predict_phot(self, models, models_err, models_mask, logwt=None):
+        """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
+        mean and variance of ``scale * model flux`` per band under the rows, the model errors added as the law of total variance,
+        masked model bands left out per band (``share``: the weight that was not).  The fitted scales are used when they are kept."""
+        from .pdf import posterior_moments
+        if len(models) != self.NMODEL:
+            raise ValueError("%d models for fits over %d" % (len(models), self.NMODEL))
+        return posterior_moments(self._rows(logwt), models, models_err, models_mask, scale=self.fit_scale, neighbors=self.neighbors,
+                                 Nneighbors=self.Nneighbors, return_share=True, device=self._device)

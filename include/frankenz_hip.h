@@ -593,6 +593,37 @@ int  fz_fit_sparse(fz_ctx* ctx, double* x, double* xe, double* xm, int64_t N, co
                    double lncut, int64_t* neighbors, int64_t* nnbr, double* lnprior, double* lnlike, double* lnprob, double* chi2,
                    int64_t* ndim, double* scale, double* scale_err, double* lmap, double* levid, double* lnkept);
 
+/* ---- posterior moments of per-model values, and the zero-point sums (extension, no reference counterpart; docs/predictive.md) ----
+ * The law.  A row r[0..n) of ln-weights with model indices j_t (dense rows: j_t = t, n = M), optional scales s_t (absent: 1), a value
+ * table V (M, L), an optional error table Ve (M, L) and an optional mask table Vm (M, L; non-zero: usable).  A nan among the counted
+ * entries, or a max m that is not finite (n = 0 included), means the row has no posterior (the rule of fz_draw_logwt and fz_mw_sweep):
+ * every output of the row is nan, its share 0, and it is counted in nskip.  Otherwise w_t = exp(r_t - m); an entry with w_t == 0
+ * contributes nothing at all (not 0 * inf); Z = sum w_t; column l includes the entries with w_t > 0 and Vm[j_t][l] != 0;
+ * c_tl = s_t V[j_t][l] (one rounding), and over the included entries
+ *     Z_l     = sum w_t                      share_l = Z_l / Z                     mean_l = sum w_t c_tl / Z_l
+ *     var_l   = sum w_t (c_tl - mean_l)^2 / Z_l  [+ sum w_t (s_t Ve[j_t][l])^2 / Z_l   with Ve]
+ * -- the CENTRAL form of the law of total variance.  Z_l == 0: mean_l = var_l = nan, share_l = 0.  Entries past nnbr[i] are never
+ * read.  Every sum is formed in one fixed order that depends on the row alone (thread q of the object's 64 or 256 adds the entries
+ * q, q + 64 [256], ... in order; one xor butterfly over the lanes; the wave sums in wave order): the same bits whatever the chunking
+ * under the workspace limit, the object order, the number of objects in the call, and host or device arguments.
+ * Refusals, before anything is gathered: an index outside [0, M) within the count, or a count outside [0, W]: -3; L < 1: -4; L > 32
+ * (FZ_MOM_LMAX, the band limit), W > 2^20 (FZ_DRAW_LMAX) or M >= 2^31: -5; dense rows with W != M: -4.
+ *
+ * fz_row_moments -- rows (N, W), neighbors (N, W) int64 and nnbr (N) int64 (both NULL: dense rows), scale (N, W) or NULL, mean (N, L),
+ *   var (N, L) or NULL, share (N, L) or NULL: host or device, staged in chunks from the workspace limit.  values, value_errs (or NULL),
+ *   value_mask (or NULL): (M, L), host or device.  nskip: one int64.
+ * fz_phot_sums -- x, xe, xm, mean, var (N, B), host or device, staged in chunks of whole strips.  Per band b over the objects with
+ *   xm != 0 and finite x, xe, p = mean, v = var:  omega = 1 / (xe^2 + v), d = x - p;  A = sum omega x p, B = sum omega p^2,
+ *   C = sum omega d^2, n = their number.  clip > 0: an object-band with omega d^2 > clip^2 is left out of all four and counted in
+ *   nclip (clip == 0: off; negative or nan: -4).  sums (3, B) float64 = A, B, C; counts (2, B) int64 = n, nclip.  Partial sums run
+ *   over strips of 1024 objects counted from object 0 (thread t adds objects t, t + 256, ... of its strip, then a halving tree) and
+ *   the strip sums are added in index order: chunking does not change a bit.  B < 1: -4; B > 32: -5. */
+int  fz_row_moments(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr,
+                    const double* scale, int64_t M, int32_t L, const double* values, const double* value_errs, const double* value_mask,
+                    double* mean, double* var, double* share, int64_t* nskip);
+int  fz_phot_sums(fz_ctx* ctx, const double* x, const double* xe, const double* xm, const double* mean, const double* var, int64_t N,
+                  int32_t B, double clip, double* sums, int64_t* counts);
+
 /* ---- Monte-Carlo draws of the k-NN fitter on the device (extension; docs/knn.md, knn.py:158-188 / 830-832) ----
  * The reference draws its K feature sets (knn.py:158-188) and every object's query features (knn.py:830-832) with NumPy's normal and
  * maps them to magnitudes / luptitudes.  Here the variates are Philox4x32-10: one call gives two standard normals by Box-Muller
