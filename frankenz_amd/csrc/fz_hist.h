@@ -89,6 +89,48 @@ namespace fz {
 #define FZ_HIST_SEAM 1           // the tile's wait + barrier stand in front of its LAST group, whose prefetch slot reads the first group of the
                                  // NEXT tile: the next tile starts from registers instead of with an exposed LDS read behind a barrier
 #endif
+#ifndef FZ_HIST_PRIO
+#define FZ_HIST_PRIO 1           // > 0: the headline's waves change their issue priority (s_setprio) with their progress through the interval between
+                                 // two tile barriers, so that a SIMD's four waves arrive there together (docs/k_hist.md, "Waves of a SIMD kept in
+                                 // step"; the policies are hist_prio_level's, 1 is the one measured best).  No arithmetic, operand or order
+                                 // changes.  0: the code without it
+#endif
+// The priority of a step by its place in the barrier interval (pos 0: the step that follows the tile barrier, the tile's last group with the seam;
+// pos 5: the last step in front of the next barrier).  Policies 4 and 5 are controls that do not look at progress (set per round / per tile).
+constexpr int hist_prio_level(int policy, int pos) {
+    return policy == 1 ? (pos < 2 ? 3 : (pos < 4 ? 2 : (pos < 5 ? 1 : 0)))      // fine: 3, 3, 2, 2, 1, 0
+         : policy == 2 ? (pos < 3 ? 1 : 0)                                       // coarse: the first half of the interval
+         : policy == 3 ? (pos < 2 ? 1 : 0)                                       // catch-up only: the two steps behind the barrier
+         : 0;
+}
+// The other forms (4-8 bands) have the barrier BEHIND the tile's last group and tiles of 6, 4 or 2 steps: the fine policy spread over the tile's
+// steps (6: 3, 3, 2, 2, 1, 0; 4: 3, 2, 1, 0; 2: 3, 0).  FZ_HIST_PRIO_FORMS says which of them take it, one bit per form: 1 the screen form
+// without the seam (per-model errors; band-constant errors at 7 and 8 bands), 2 per-object band counts, 4 the direct forms (mode B, broad
+// likelihoods), 8 the segmented kernels' loop over pure tiles, 16 the headline's siblings at 4 and 6 bands (the headline's own placement).
+// A form is in the default if its registers, spills and scratch stayed what they were and its timing gained (docs/k_hist.md has each).
+#ifndef FZ_HIST_PRIO_FORMS
+#define FZ_HIST_PRIO_FORMS (2 | 4 | 8 | 16)
+#endif
+constexpr int hist_prio_step(int pos, int ns) { return ns < 2 ? 0 : (3 * (ns - 1 - pos) + ns - 2) / (ns - 1); }
+// s_setprio takes a literal: the level is a constant after unrolling (policies 1-3) or wave-uniform in a scalar register (4, 5: a scalar branch)
+__device__ __forceinline__ void hist_setprio(int p) {
+    switch (p) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+// development build (-DFZ_HIST_WSTATS, tools/devbuild.sh): where the waves of the headline's instantiation wait.  Every wave sums cycle-counter
+// differences over the launch in scalar registers -- (a) at the tile barrier, (b) at the two __syncthreads() of a round, (c) in the finish, (d) in
+// the prologue up to the first barrier, and its whole life -- and adds them at the end to its wave index's row of this table, which the launcher
+// prints and clears per launch (fz_launch.h).  The last four words count the SIMD the wave ran on (HW_ID), to check which waves share one.
+#ifdef FZ_HIST_WSTATS
+static __device__ unsigned long long fz_hwstats[16 * 12];
+#define FZ_HIST_WSTATS_ON 1
+#else
+#define FZ_HIST_WSTATS_ON 0
+#endif
 // fma(a, b, c) as ONE three-address v_fma_f64 (same operands, same single rounding).  For the places where c is a constant that
 // lives in a register pair across the model loop: the compiler forms those as v_mov_b64 tmp, c + v_fmac_f64 tmp, a, b -- a copy per
 // use that computes nothing.  Not volatile: the scheduler stays free to move it.
@@ -359,6 +401,19 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     const int64_t N = a_.N;                                             // (the launch's geometry below; the prologue and the finish ask hq())
     constexpr int TILE = hist_tile<SRC>(), RW = SRC::RW, TDR = RW * TILE, TD = TDR + TILE / 2, NT = NW * 64, OD = SRC::OBJ_DOUBLES;
     constexpr int WP = SRC::WPOW, BT = SRC::NB;
+    // FZ_HIST_PRIO: the headline's instantiation only (six steps between two barriers; the other forms were not measured with it)
+    constexpr int PRIO = (SEAM && TILE == 384 && (BT == 5 || (FZ_HIST_PRIO_FORMS & 16))) ? FZ_HIST_PRIO : 0;
+    // ... and the forms of FZ_HIST_PRIO_FORMS (4-8 bands, the loop over "pure" tiles): priority by the step's place in its tile
+    constexpr int PFORM = SEG ? 8 : (OBJK ? 2 : (EXACT ? 4 : 1));
+    // (two instantiations spill more with it -- the segmented screen form with per-model errors at 4 bands, 20 B of scratch more per lane, and
+    //  per-object band counts at 8 bands, 12 B more -- and keep the parent's code)
+    constexpr bool PWORSE = (SEG && !EXACT && SRC::LMODE == 0 && BT == 4) || (OBJK && !SEG && !EXACT && BT == 8);
+    constexpr bool PRIOF = (FZ_HIST_PRIO > 0) && !SEAM && BT <= 8 && (FZ_HIST_PRIO_FORMS & PFORM) != 0 && !PWORSE;
+    // FZ_HIST_WSTATS: the instantiations that have the seam; sums in scalar registers (the cycle counter is a scalar read)
+    constexpr bool WST = (FZ_HIST_WSTATS_ON == 1) && SEAM;
+    [[maybe_unused]] unsigned long long wst_a = 0, wst_b = 0, wst_c = 0, wst_d = 0;
+    auto wclk = [&]() -> unsigned long long { if constexpr (WST) return __builtin_readcyclecounter(); else return 0ull; };
+    [[maybe_unused]] const unsigned long long wst_life = wclk();
     static_assert(!OBJK || TW == 1, "per-object band counts: one object per wave");
     static_assert(!SEG || (OBJK && SRC::NB <= 8), "segments: run-time band counts, 4-8 bands");
     constexpr double SEG_VBIG = BT <= 5 ? 0x1p192 : (BT == 6 ? 0x1p160 : (BT == 7 ? 0x1p137 : 0x1p120));      // 2^(960 / BT): BT such terms multiply without overflow
@@ -463,6 +518,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     for (int64_t rnd = 0; rnd < nrounds; ++rnd) {
         const int64_t g = gw + rnd * nwaves;
         const bool work = g < ngroups;                            // wave-uniform
+        [[maybe_unused]] const unsigned long long wst_r0 = wclk();
         const int64_t i0 = work ? g * TW : 0;
         const HistArgs<SRC>& hp = hq();                             // the prologue's view of the arguments
         [[maybe_unused]] const SRC& srcp = hp.src;                  // (same values as `src`; the objects' pointers are read here, per object)
@@ -541,6 +597,11 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
         int tid0 = tid;
         if constexpr (SEAM) asm volatile("" : "+v"(tid0));
         nl_stage_tile<SRC, TILE, NT, true>(src, posw, 0, tileA, tid0, wave);
+        if constexpr (WST) {
+            const unsigned long long t1 = wclk();
+            __syncthreads();
+            wst_d += t1 - wst_r0; wst_b += wclk() - t1;
+        } else
         __syncthreads();
         // the wave's objects stay in VGPRs for the whole model loop (an LDS broadcast read: the compiler
         // cannot tell that they are wave-uniform and keeps them out of the scalar file)
@@ -963,6 +1024,11 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
         // the tile's wait for the staged copy + barrier (every wave meets it exactly once per tile)
         auto tile_barrier = [&]() {
 #if !defined(FZ_DIAG_NOBARRIER)
+            if constexpr (WST) {
+                const unsigned long long t0 = wclk();
+                __syncthreads();
+                wst_a += wclk() - t0;
+            } else
             __syncthreads();
 #endif
         };
@@ -1035,6 +1101,9 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                         }
                         // AHD: the reads above stay in front of the chi2 (left to itself the scheduler sinks them below it, and the next step
                         // opens with a wait for a record requested a dozen instructions earlier)
+                        if constexpr (PRIO >= 1 && PRIO <= 3) hist_setprio(hist_prio_level(PRIO, st + MP >= TILE / 64 ? 0 : st + 1));
+                        if constexpr (PRIO == 5) { if (st == 0) hist_setprio(((wave >> 2) + t) & 3); }      // (wave: a scalar, see its readfirstlane)
+                        if constexpr (PRIOF) hist_setprio(hist_prio_step(st / MP, TILE / 64 / MP));
                         if constexpr (AHD && PF) __builtin_amdgcn_sched_barrier(0);
                         step_body(m, ptag, st, t, tailc, std::false_type{}, false);
                     }
@@ -1084,6 +1153,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                 }
             }
         }
+        if constexpr (PRIO == 4) { if (work) hist_setprio(wave >> 2); }      // (the control: the youngest wave highest, for the whole round)
         if constexpr (!SEG) {
             for (int t = 0; t < ntiles; t += 2) {
                 if (t + 1 < ntiles) run_tile(tileA, tileB, t, std::false_type{}, std::false_type{}); else run_tile(tileA, tileB, t, std::true_type{}, std::false_type{});
@@ -1120,6 +1190,8 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
             }
         }
 
+        if constexpr (PRIO > 0 || PRIOF) __builtin_amdgcn_s_setprio(0);     // the round's finish and the next prologue run as before
+        [[maybe_unused]] const unsigned long long wst_f0 = wclk();
         // finish: what is left in the rings, the exact maximum, the evidence, the ambiguous entries, the PDF
         if (work) {
 #pragma unroll 1
@@ -1223,7 +1295,24 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                 kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true);
             }
         }
+        if constexpr (WST) {
+            const unsigned long long t1 = wclk();
+            __syncthreads();
+            wst_c += t1 - wst_f0; wst_b += wclk() - t1;
+        } else
         __syncthreads();
+    }
+    if constexpr (WST) {
+#ifdef FZ_HIST_WSTATS
+        const unsigned long long life = wclk() - wst_life;
+        const int simd = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);      // HW_ID bits 5:4
+        if (lane == 0 && wave < 16) {
+            unsigned long long* h = fz_hwstats + wave * 12;
+            atomicAdd(h + 0, wst_a); atomicAdd(h + 1, wst_b); atomicAdd(h + 2, wst_c); atomicAdd(h + 3, wst_d);
+            atomicAdd(h + 4, life); atomicAdd(h + 5, 1ull); atomicAdd(h + 6, (unsigned long long)nrounds);
+            atomicAdd(h + 8 + (simd & 3), 1ull);
+        }
+#endif
     }
 }
 

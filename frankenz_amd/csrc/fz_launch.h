@@ -462,6 +462,32 @@ int fz_launch_hist_g(fz_ctx* c, const SRC& src, const fz::KdeView& kv, int64_t n
                            lmap, levid, pdfs, c->d_redo.as<int>() + 1, (int*)nullptr, c->d_redo.as<int>());
     }
     HIPCHK(hipGetLastError());
+#ifdef FZ_HIST_WSTATS
+    if constexpr (!EXACT && !OBJK && !SEG && SRC::NB <= 8 && SRC::RW <= 6) {
+        // where the waves waited (fz_hist.h): per wave index the share of its life at the tile barrier (a), at the round's two
+        // __syncthreads() (b), in the finish (c) and in the prologue (d); one line per age rank (wave >> 2), four waves (SIMDs) each
+        unsigned long long h[16 * 12], z[16 * 12] = {0};
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(fz::fz_hwstats), sizeof h);
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(fz::fz_hwstats), z, sizeof z);
+        fprintf(stderr, "HWSTATS k_hist<%d bands>: n %lld M %lld, %lld blocks x %d waves\n", SRC::NB, (long long)n, (long long)M, (long long)blocks, NW);
+        for (int r = 0; r < NW / 4; ++r) {
+            double s[5] = {0, 0, 0, 0, 0};
+            char simd[128]; int q = 0;
+            for (int w = 4 * r; w < 4 * r + 4; ++w) {
+                const unsigned long long* e = h + w * 12;
+                for (int k = 0; k < 5; ++k) s[k] += (double)e[k];
+                q += snprintf(simd + q, sizeof simd - q, " w%d:%llu/%llu/%llu/%llu", w, e[8], e[9], e[10], e[11]);
+            }
+            const double life = s[4] > 0 ? s[4] : 1.0;
+            fprintf(stderr, "HWSTATS rank %d (waves %d-%d): life %.4g cycles per wave | tile barrier %.2f %% | round barriers %.2f %% | finish %.2f %% | "
+                            "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 12 + 5] ? h[4 * r * 12 + 5] : 1)),
+                    100 * s[0] / life, 100 * s[1] / life, 100 * s[2] / life, 100 * s[3] / life);
+            for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 12] / (double)(h[w * 12 + 4] ? h[w * 12 + 4] : 1));
+            fprintf(stderr, " | launches on SIMD 0/1/2/3:%s\n", simd);
+        }
+    }
+#endif
     return 0;
 }
 template <class SRC>

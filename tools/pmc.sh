@@ -3,9 +3,13 @@
 # launch shape (default 1e6 objects x 1e5 models, one launch per step), per-kernel per-launch sums, and the HBM-traffic entries
 # of profiles/pmc_latest.json (FETCH_SIZE x 2 on gfx950 for wide coalesced reads, MI355X_MICROARCH.md, + WRITE_SIZE; both in KB).
 #   BENCH_ARGS="--mode B" TAG=modeB ./tools/pmc.sh      -> gpurun_out/pmc_<TAG>.txt, gpurun_out/pmc_<TAG>.json
+#   PARENT_LIB=/path/libparent.so ./tools/pmc.sh         every pass first on that library (tag parent_<TAG>), then on the tree's: the two
+#                                                        builds alternate within the call
+# A pass that fails ends the script: nothing more is started on the GPU after it.
 export TMPDIR=/tmp
 export FZ_BENCH_NO_EXTRA=1
 TAG=${TAG:-headline}
+TAG0=$TAG
 ARGS="--nobj ${NOBJ:-1000000} --nmodel ${NMODEL:-100000} --steps 1 --warmup 1 --no-cpu ${BENCH_ARGS}"
 SETS=(
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"
@@ -18,8 +22,12 @@ SETS=(
 i=0
 for set in "${SETS[@]}"; do
   i=$((i+1))
+  for T in ${PARENT_LIB:+parent_$TAG0} $TAG0; do (
+  TAG=$T; if [ $T != $TAG0 ]; then export FRANKENZ_HIP_LIB=$PARENT_LIB; fi
   rocprofv3 --kernel-trace --pmc $set --output-format csv -d gpurun_out/pmc_${TAG}_$i -- python3 bench.py $ARGS > gpurun_out/pmc_${TAG}_$i.log 2>&1
+  ) || { echo "pmc.sh: pass $i of $T failed"; exit 1; }; done
 done
+for TAG in ${PARENT_LIB:+parent_$TAG0} $TAG0; do
 python3 - "$TAG" "$ARGS" <<'PY' | tee gpurun_out/pmc_${TAG}.txt
 import csv, glob, collections, sys, json
 tag, args = sys.argv[1], sys.argv[2]
@@ -45,3 +53,4 @@ sys.path.insert(0, '.')
 from frankenz_amd._lib import source_id
 json.dump({'bench_args': args, 'source_id': source_id(), 'kernels': out}, open('gpurun_out/pmc_%s.json' % tag, 'w'), indent=1)
 PY
+done
