@@ -1187,7 +1187,7 @@ static int fit_predict_impl(fz_ctx* c, double* x, double* xe, double* xm, int64_
             if (cdf) {
                 FZCHK(run_cdf(c, n, (int)M, M, lpl, nullptr, nullptr, 1, ko, d_pdf, d_lm, d_le));
             } else {
-                FZCHK(fz_launch_plane_predict(c, lpl, n, M, 0, ko, d_lm, d_le, d_pdf));
+                FZCHK(fz_launch_plane_predict(fz_call{c, n, M, ko, d_lm, d_le, d_pdf}, lpl, 0));
             }
         } else {
             const int r = fitpredict_special_forms(c, mode, var, o->dim_prior, n, ko, d_lm, d_le, d_pdf);
@@ -1239,7 +1239,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
         const double* d_in; double* d_pdf; double* d_lm; double* d_le;
         FZCHK(inv.at(i0, n, &d_in)); FZCHK(pdv.at(i0, n, &d_pdf)); FZCHK(lmv.at(i0, n, &d_lm)); FZCHK(lev.at(i0, n, &d_le));
         if (!ko->use_wt_thresh) FZCHK(run_cdf(c, n, (int)M, M, d_in, nullptr, nullptr, is_log ? 1 : 0, ko, d_pdf, d_lm, d_le));
-        else FZCHK(fz_launch_plane_predict(c, d_in, n, M, linear, ko, d_lm, d_le, d_pdf));
+        else FZCHK(fz_launch_plane_predict(fz_call{c, n, M, ko, d_lm, d_le, d_pdf}, d_in, linear));
         FZCHK(pdv.back(i0, n)); FZCHK(lmv.back(i0, n));
         if (is_log) FZCHK(lev.back(i0, n));
         return 0;

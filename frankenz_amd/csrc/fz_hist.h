@@ -124,10 +124,35 @@ __device__ __forceinline__ void hist_setprio(int p) {
 // development build (-DFZ_HIST_WSTATS, tools/devbuild.sh): where the waves of the headline's instantiation wait.  Every wave sums cycle-counter
 // differences over the launch in scalar registers -- (a) at the tile barrier, (b) at the two __syncthreads() of a round, (c) in the finish, (d) in
 // the prologue up to the first barrier, and its whole life -- and adds them at the end to its wave index's row of this table, which the launcher
-// prints and clears per launch (fz_launch.h).  The last four words count the SIMD the wave ran on (HW_ID), to check which waves share one.
+// has printed and cleared per launch (hist_wstats_print below).  The last four words count the SIMD the wave ran on (HW_ID), to check which waves share one.
 #ifdef FZ_HIST_WSTATS
 static __device__ unsigned long long fz_hwstats[16 * 12];
 #define FZ_HIST_WSTATS_ON 1
+// where the waves waited: per wave index the share of its life at the tile barrier (a), at the round's two __syncthreads() (b), in
+// the finish (c) and in the prologue (d); one line per age rank (wave >> 2), four waves (SIMDs) each.  Waits for the launch on
+// `stream`, prints the table and clears it
+inline void hist_wstats_print(hipStream_t stream, int nb, long long n, long long M, long long blocks, int nw) {
+    unsigned long long h[16 * 12], z[16 * 12] = {0};
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(fz_hwstats), sizeof h);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(fz_hwstats), z, sizeof z);
+    fprintf(stderr, "HWSTATS k_hist<%d bands>: n %lld M %lld, %lld blocks x %d waves\n", nb, n, M, blocks, nw);
+    for (int r = 0; r < nw / 4; ++r) {
+        double s[5] = {0, 0, 0, 0, 0};
+        char simd[128]; int q = 0;
+        for (int w = 4 * r; w < 4 * r + 4; ++w) {
+            const unsigned long long* e = h + w * 12;
+            for (int k = 0; k < 5; ++k) s[k] += (double)e[k];
+            q += snprintf(simd + q, sizeof simd - q, " w%d:%llu/%llu/%llu/%llu", w, e[8], e[9], e[10], e[11]);
+        }
+        const double life = s[4] > 0 ? s[4] : 1.0;
+        fprintf(stderr, "HWSTATS rank %d (waves %d-%d): life %.4g cycles per wave | tile barrier %.2f %% | round barriers %.2f %% | finish %.2f %% | "
+                        "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 12 + 5] ? h[4 * r * 12 + 5] : 1)),
+                100 * s[0] / life, 100 * s[1] / life, 100 * s[2] / life, 100 * s[3] / life);
+        for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 12] / (double)(h[w * 12 + 4] ? h[w * 12 + 4] : 1));
+        fprintf(stderr, " | launches on SIMD 0/1/2/3:%s\n", simd);
+    }
+}
 #else
 #define FZ_HIST_WSTATS_ON 0
 #endif

@@ -90,15 +90,14 @@ static int fz_planes_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, 
 
 static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t n, const fz_kde_opts* ko, double* lmap, double* levid,
                             double* pdfs) {
-    const int64_t M = c->M;
+    const fz_call a{c, n, c->M, ko, lmap, levid, pdfs};
 #if FZ_EXACT_BT
     if (var == VAR_SEG) {
         // masked models / unobserved object bands against per-model errors: k_hist on the segmented model layout (mask-free arithmetic,
         // the handed-back objects are swept by the masked variant); +1: not applicable, the caller takes the masked route
         const int r = with_mode(mode, [&](auto MODE) -> int {
             constexpr int MD = decltype(MODE)::value;
-            return fz_launch_hist_seg(c, phot_src<MD, VAR_FAST>(c, dim_prior), phot_src<MD, VAR_MASKED>(c, dim_prior), n, M, ko, lmap,
-                                      levid, pdfs);
+            return fz_launch_hist_seg(a, phot_src<MD, VAR_FAST>(c, dim_prior), phot_src<MD, VAR_MASKED>(c, dim_prior));
         });
         return r < 0 ? r : (r == 0 ? 0 : 1);
     }
@@ -114,8 +113,7 @@ static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t
         const int r = with_mode(mode, [&](auto MODE) -> int {
             constexpr int MD = decltype(MODE)::value;
             if constexpr (MD == 0) return 1;                     // (the form is not compiled for mode A)
-            else return fz_launch_hist_objmask(c, phot_src<MD, VAR_FAST>(c, dim_prior), phot_src<MD, VAR_MASKED>(c, dim_prior), n, M, ko,
-                                               lmap, levid, pdfs);
+            else return fz_launch_hist_objmask(a, phot_src<MD, VAR_FAST>(c, dim_prior), phot_src<MD, VAR_MASKED>(c, dim_prior));
         });
         if (var == VAR_OBJMASK) return r < 0 ? r : (r == 0 ? 0 : 1);
         if (r <= 0) return r;
@@ -129,7 +127,7 @@ static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t
     // masks, a prior, the KDE forms k_hist does not take -- runs the masked variants
     if ((var == VAR_FAST || var == VAR_PAD) && !c->prior.tab) {
         const int r = with_mode(mode, [&](auto MODE) -> int {
-            return fz_launch_hist_only(c, phot_src<decltype(MODE)::value, VAR_FAST>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
+            return fz_launch_hist_only(a, phot_src<decltype(MODE)::value, VAR_FAST>(c, dim_prior));
         });
         if (r <= 0) return r;
     }
@@ -137,10 +135,10 @@ static int fz_fitpredict_bt(fz_ctx* c, int mode, int var, int dim_prior, int64_t
     return with_mode_var(mode, var, [&](auto MODE, auto VAR) -> int {
         constexpr int MD = decltype(MODE)::value, VR = decltype(VAR)::value;
 #if !defined(FZ_DEV_FAST)
-        if (c->prior.tab && c->prior.frac) return fz_launch_fitpredict(c, phot_src<MD, VR, 2>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
-        if (c->prior.tab) return fz_launch_fitpredict(c, phot_src<MD, VR, 1>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
+        if (c->prior.tab && c->prior.frac) return fz_launch_fitpredict(a, phot_src<MD, VR, 2>(c, dim_prior));
+        if (c->prior.tab) return fz_launch_fitpredict(a, phot_src<MD, VR, 1>(c, dim_prior));
 #endif
-        return fz_launch_fitpredict(c, phot_src<MD, VR>(c, dim_prior), n, M, ko, lmap, levid, pdfs);
+        return fz_launch_fitpredict(a, phot_src<MD, VR>(c, dim_prior));
     });
 }
 

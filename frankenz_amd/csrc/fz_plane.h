@@ -83,6 +83,18 @@ typedef double plane_d4 __attribute__((ext_vector_type(4)));
 #ifdef FZ_PLANE_STATS
 __device__ unsigned long long fz_plstats[16];
 #define PLT(i) do { const long long plt_ = (long long)clock64(); pltime[i] += plt_ - pllast; pllast = plt_; } while (0)
+// waits for the launch on `stream`, prints its sums and clears them
+inline void plane_stats_print(hipStream_t stream, int nw, int e2) {
+    unsigned long long h[16], z[16] = {0};
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(fz_plstats), sizeof h);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(fz_plstats), z, sizeof z);
+    const double wr = h[1] ? (double)h[1] : 1.0;                 // wave-rows
+    fprintf(stderr, "PLSTATS k_plane_rows<%d,%d>: %llu waves, %.1f rows each | cycles per wave and row: wait for the row %.0f | maximum + post %.0f | "
+                    "barrier %.0f | clear + previous row's sums / ties %.0f | weigh %.0f | request + sums + post %.0f | epilogue (all waves) %.0f "
+                    "(waves with outputs: %.0f)\n", nw, e2, h[0], wr / (double)(h[0] ? h[0] : 1), h[2] / wr, h[3] / wr, h[4] / wr, h[5] / wr, h[6] / wr,
+            h[7] / wr, h[8] / wr, h[9] ? h[10] / (wr * (double)h[9] / (double)h[0]) : 0.0);
+}
 #else
 #define PLT(i) do { } while (0)
 #endif

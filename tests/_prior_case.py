@@ -93,8 +93,8 @@ TWOPASS_LIMIT = 1 << 20                                      # the smallest work
 def twopass_objects(M):
     """How many objects it takes at TWOPASS_LIMIT for a chunk of n < cu_count * 64 objects to lose its candidate lists and run the
     two-pass kernels.  fz_launch_fused_wm at (TW, NW) = (1, 4): ``per_wave = TW * M * sizeof(Cand)`` (16 bytes each), ``need =
-    (groups + NW - 1) / NW``, ``fit = ws_limit / (per_wave * NW)`` and, while ``need <= cu_count``, ``else if (fit < need) return
-    1;``.  At 1 MiB fit = 16384 / M: 252, 127, 63 at M = 65, 129, 257.  203 objects need 51 blocks, which fit at every one of
+    (groups + NW - 1) / NW``, ``fit = ws_limit / (per_wave * NW)`` and, while ``need <= cu_count``, +1 when ``fit < need``
+    (fz_grid_resident, csrc/fz_grid.h).  At 1 MiB fit = 16384 / M: 252, 127, 63 at M = 65, 129, 257.  203 objects need 51 blocks, which fit at every one of
     these model counts, so the fallback runs take 4 fit + 3 objects instead (need = fit + 1 <= 253 blocks; three objects in the
     last one): 1011, 511, 255.  A single model's lists always fit (fit = 16384 blocks): that case stays at 203 objects and k_fused."""
     if M == 1:

@@ -483,7 +483,7 @@ def test_band_constant_model_errors_take_the_hoisted_path(kw, errs, monkeypatch)
 @pytest.mark.parametrize('env', [{'FZ_HIST': '0', 'FZ_FUSED_CFG': '4,8'}, {'FZ_HIST': '0', 'FZ_FUSED_CFG': '2,8'}, {'FZ_HIST': '0', 'FZ_FUSED_CFG': '2,16'},
                                  {'FZ_HIST': '0', 'FZ_FUSED_CFG': '1,4'}, {'FZ_HIST': '0', 'FZ_NO_WSPACE': '1'}, {'FZ_CHUNK': '5000'},
                                  {'FZ_HIST': '0', 'FZ_NO_WSPACE': '1', 'FZ_FUSED_CFG': '2,16'}, {'FZ_HIST': '0'},
-                                 {'FZ_NOLIST': '1'}, {'FZ_EXACT_EVIDENCE': '1'},
+                                 {'FZ_HIST': '0', 'FZ_FUSED_CFG': '2,12'}, {'FZ_NOLIST': '1'}, {'FZ_EXACT_EVIDENCE': '1'},
                                  {'FZ_HIST_AMBCAP': '3'}, {'FZ_HIST_AMBCAP': '3', 'FZ_NOLIST': '1'}])      # ambiguous lists of 3 entries: (nearly) every object overflows and is re-run by the exact sweep
 def test_tuning_switches_do_not_change_results(env, monkeypatch):
     """every launch geometry / kernel body / chunking reachable through the diagnostic
@@ -508,6 +508,31 @@ def test_tuning_switches_do_not_change_results(env, monkeypatch):
         close(p1, p0, rtol=1e-9, atol=1e-15); close(lm1, lm0, rtol=1e-12); close(le1, le0, **EVID)
     rp, rlm, rle = fo.bruteforce_fit_predict(X[:30].copy(), Xe[:30].copy(), Xm[:30].copy(), Y, Ye, Ym, z, ze, label_dict=od, **kw)
     close(p1[:30], rp, rtol=1e-8, atol=1e-14)
+
+
+def test_fused_cfg_that_is_not_instantiated_is_refused(monkeypatch):
+    """FZ_FUSED_CFG names a geometry that was not compiled: the call is refused with that text as a Python exception, and the
+    next call on the same engine runs as if nothing had happened (same shape as test_tuning_switches_do_not_change_results)."""
+    from frankenz_amd import BruteForce
+    d, od = dicts()
+    rs = np.random.RandomState(123)
+    M, N, B = 777, 16500, 5
+    Y = rs.lognormal(1., 1., size=(M, B)) * 3; Ye = Y * rs.uniform(0.02, 0.08, size=(M, B)); Ym = np.ones((M, B))
+    X = Y[rs.choice(M, N)] + SDSS5 * rs.randn(N, B); Xe = np.tile(SDSS5, (N, 1)); Xm = np.ones((N, B))
+    z = rs.uniform(0, 6, M); ze = np.full(M, 0.05)
+    run = lambda: BruteForce(Y, Ye, Ym).fit_predict(X.copy(), Xe.copy(), Xm.copy(), z, ze, label_dict=d, return_gof=True,
+                                                    save_fits=False, verbose=False)
+    p0, (lm0, le0) = run()
+    monkeypatch.setenv('FZ_HIST', '0')
+    monkeypatch.setenv('FZ_FUSED_CFG', '3,3')
+    with pytest.raises(RuntimeError, match=r'FZ_FUSED_CFG=3,3 is not an instantiated configuration'):
+        run()
+    monkeypatch.delenv('FZ_FUSED_CFG')
+    p1, (lm1, le1) = run()                                       # k_fused at its own geometry
+    monkeypatch.delenv('FZ_HIST')
+    p2, (lm2, le2) = run()                                       # the default form again
+    close(p1, p0, rtol=1e-9, atol=1e-15); close(lm1, lm0, rtol=1e-12); close(le1, le0, **EVID)
+    close(p2, p0, rtol=1e-9, atol=1e-15); close(lm2, lm0, rtol=1e-12); close(le2, le0, rtol=1e-12)
 
 
 @pytest.mark.parametrize('kw', [{}, {'ignore_model_err': True}, {'free_scale': True, 'ignore_model_err': True}])
