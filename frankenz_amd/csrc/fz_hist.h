@@ -89,6 +89,11 @@ namespace fz {
 #define FZ_HIST_SEAM 1           // the tile's wait + barrier stand in front of its LAST group, whose prefetch slot reads the first group of the
                                  // NEXT tile: the next tile starts from registers instead of with an exposed LDS read behind a barrier
 #endif
+#ifndef FZ_HIST_FINISH
+#define FZ_HIST_FINISH 1         // the per-object finish convolves with a lane per block of 12 outputs and issues the reads of its two division loops
+                                 // together (hist_finish_row, fz_kernels.h; docs/k_hist.md, "The finish"): the same operations on the same operands
+                                 // in the same order as kde_finalize, which every other kernel keeps.  0: the code without it
+#endif
 #ifndef FZ_HIST_PRIO
 #define FZ_HIST_PRIO 1           // > 0: the headline's waves change their issue priority (s_setprio) with their progress through the interval between
                                  // two tile barriers, so that a SIMD's four waves arrive there together (docs/k_hist.md, "Waves of a SIMD kept in
@@ -126,31 +131,36 @@ __device__ __forceinline__ void hist_setprio(int p) {
 // the prologue up to the first barrier, and its whole life -- and adds them at the end to its wave index's row of this table, which the launcher
 // has printed and cleared per launch (hist_wstats_print below).  The last four words count the SIMD the wave ran on (HW_ID), to check which waves share one.
 #ifdef FZ_HIST_WSTATS
-static __device__ unsigned long long fz_hwstats[16 * 12];
+static __device__ unsigned long long fz_hwstats[16 * 16];
 #define FZ_HIST_WSTATS_ON 1
 // where the waves waited: per wave index the share of its life at the tile barrier (a), at the round's two __syncthreads() (b), in
 // the finish (c) and in the prologue (d); one line per age rank (wave >> 2), four waves (SIMDs) each.  Waits for the launch on
 // `stream`, prints the table and clears it
 inline void hist_wstats_print(hipStream_t stream, int nb, long long n, long long M, long long blocks, int nw) {
-    unsigned long long h[16 * 12], z[16 * 12] = {0};
+    unsigned long long h[16 * 16], z[16 * 16] = {0};
     (void)hipStreamSynchronize(stream);
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(fz_hwstats), sizeof h);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(fz_hwstats), z, sizeof z);
     fprintf(stderr, "HWSTATS k_hist<%d bands>: n %lld M %lld, %lld blocks x %d waves\n", nb, n, M, blocks, nw);
     for (int r = 0; r < nw / 4; ++r) {
-        double s[5] = {0, 0, 0, 0, 0};
+        double s[5] = {0, 0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
         char simd[128]; int q = 0;
         for (int w = 4 * r; w < 4 * r + 4; ++w) {
-            const unsigned long long* e = h + w * 12;
+            const unsigned long long* e = h + w * 16;
             for (int k = 0; k < 5; ++k) s[k] += (double)e[k];
+            for (int k = 0; k < 4; ++k) c[k] += (double)e[12 + k];
             q += snprintf(simd + q, sizeof simd - q, " w%d:%llu/%llu/%llu/%llu", w, e[8], e[9], e[10], e[11]);
         }
         const double life = s[4] > 0 ? s[4] : 1.0;
         fprintf(stderr, "HWSTATS rank %d (waves %d-%d): life %.4g cycles per wave | tile barrier %.2f %% | round barriers %.2f %% | finish %.2f %% | "
-                        "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 12 + 5] ? h[4 * r * 12 + 5] : 1)),
+                        "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 16 + 5] ? h[4 * r * 16 + 5] : 1)),
                 100 * s[0] / life, 100 * s[1] / life, 100 * s[2] / life, 100 * s[3] / life);
-        for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 12] / (double)(h[w * 12 + 4] ? h[w * 12 + 4] : 1));
+        for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 16] / (double)(h[w * 16 + 4] ? h[w * 16 + 4] : 1));
         fprintf(stderr, " | launches on SIMD 0/1/2/3:%s\n", simd);
+        // the finish by its parts: c1 last drains, reductions, logarithms, ambiguous band, ln-max / ln-evidence; c2 the division by the kernel
+        // mass; c3 the convolution and the parked outputs; c4 the total, the normalisation and the stores
+        fprintf(stderr, "HWSTATS rank %d finish: c1 %.2f %% | c2 %.2f %% | c3 %.2f %% | c4 %.2f %% of the waves' life\n", r,
+                100 * c[0] / life, 100 * c[1] / life, 100 * c[2] / life, 100 * c[3] / life);
     }
 }
 #else
@@ -439,6 +449,16 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     [[maybe_unused]] unsigned long long wst_a = 0, wst_b = 0, wst_c = 0, wst_d = 0;
     auto wclk = [&]() -> unsigned long long { if constexpr (WST) return __builtin_readcyclecounter(); else return 0ull; };
     [[maybe_unused]] const unsigned long long wst_life = wclk();
+    // (c) by its parts: wmark(k) closes part k of the finish (1 .. 4, hist_wstats_print names them)
+    [[maybe_unused]] unsigned long long wst_cp[4] = {0, 0, 0, 0}, wst_last = 0;
+    [[maybe_unused]] auto wmark = [&](int k) {
+        if constexpr (WST) { const unsigned long long now = wclk(); wst_cp[k - 1] += now - wst_last; wst_last = now; }
+    };
+    // FZ_HIST_FINISH: the forms with band-constant errors and compile-time band counts at 4 and 5 bands -- the headline, its 4-band
+    // sibling and the direct form of the broad likelihoods: no vector spill and no scratch with it, and faster.  The free scale (mode B)
+    // gained nothing; per-model errors, per-object band counts and the segmented kernels spill more vector registers with it, as does
+    // the direct form at 6 bands; 7 and 8 bands were not tabulated (docs/k_hist.md, "The finish", has the table): they keep the parent's call
+    constexpr bool FIN = (FZ_HIST_FINISH == 1) && !SEG && !OBJK && SRC::LMODE == 1 && SRC::NB <= 5;
     static_assert(!OBJK || TW == 1, "per-object band counts: one object per wave");
     static_assert(!SEG || (OBJK && SRC::NB <= 8), "segments: run-time band counts, 4-8 bands");
     constexpr double SEG_VBIG = BT <= 5 ? 0x1p192 : (BT == 6 ? 0x1p160 : (BT == 7 ? 0x1p137 : 0x1p120));      // 2^(960 / BT): BT such terms multiply without overflow
@@ -1217,6 +1237,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
 
         if constexpr (PRIO > 0 || PRIOF) __builtin_amdgcn_s_setprio(0);     // the round's finish and the next prologue run as before
         [[maybe_unused]] const unsigned long long wst_f0 = wclk();
+        if constexpr (WST) wst_last = wst_f0;
         // finish: what is left in the rings, the exact maximum, the evidence, the ambiguous entries, the PDF
         if (work) {
 #pragma unroll 1
@@ -1317,7 +1338,12 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                         continue;
                     }
                 }
-                kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true);
+                if constexpr (WST) {
+                    if constexpr (FIN) hist_finish_row<12>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, wmark);
+                    else kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true, wmark);
+                    wmark(4);
+                } else if constexpr (FIN) hist_finish_row<12>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0);
+                else kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true);
             }
         }
         if constexpr (WST) {
@@ -1332,10 +1358,11 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
         const unsigned long long life = wclk() - wst_life;
         const int simd = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);      // HW_ID bits 5:4
         if (lane == 0 && wave < 16) {
-            unsigned long long* h = fz_hwstats + wave * 12;
+            unsigned long long* h = fz_hwstats + wave * 16;
             atomicAdd(h + 0, wst_a); atomicAdd(h + 1, wst_b); atomicAdd(h + 2, wst_c); atomicAdd(h + 3, wst_d);
             atomicAdd(h + 4, life); atomicAdd(h + 5, 1ull); atomicAdd(h + 6, (unsigned long long)nrounds);
             atomicAdd(h + 8 + (simd & 3), 1ull);
+            for (int k = 0; k < 4; ++k) atomicAdd(h + 12 + k, wst_cp[k]);
         }
 #endif
     }

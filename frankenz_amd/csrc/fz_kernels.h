@@ -389,15 +389,19 @@ __device__ __forceinline__ void kde_scatter(const KdeView& kv, double* row, bool
 // own reference instead of the evidence; a normalised PDF does not see the difference)
 // bymass: the histogram holds plain weight sums per index; the division by the kernel mass of the
 // index (kv.normtab) happens here, once per index instead of once per stacked model.
-template <bool HO = false>
+// MK: a development build's time stamps between the parts (k_hist's FZ_HIST_WSTATS); the default does nothing and leaves no code
+struct NoMark { __device__ __forceinline__ void operator()(int) const {} };
+template <bool HO = false, class MK = NoMark>
 __device__ __forceinline__ void kde_finalize(const KdeView& kv, double* row, bool ok, int normalize,
-                                             double* out, int lane, double scale = 1.0, bool bymass = false) {
+                                             double* out, int lane, double scale = 1.0, bool bymass = false, MK mk = MK{}) {
     const int G = (int)kv.G;
     if (!ok) { for (int t = lane; t < G; t += 64) out[t] = NAN; return; }
     double tot = 0.0;
     if (HO || kv.kmode == KDE_HIST) {
         const int w2 = 2 * kv.w0;
+        mk(1);
         if (bymass) { for (int k = lane; k < G + w2; k += 64) row[k] = row[k] / kv.normtab[k]; }
+        mk(2);
         const double* kr = kv.kern + kv.koff0;
         if (w2 < 128) {
             // the dictionary kernel (w2 + 1 taps) sits in two registers across the wave -- one coalesced
@@ -427,6 +431,7 @@ __device__ __forceinline__ void kde_finalize(const KdeView& kv, double* row, boo
                 if (normalize) { row[t] = v0; if (two) row[t + 64] = v1; }
                 else { out[t] = v0 * scale; if (two) out[t + 64] = v1 * scale; }
             }
+            mk(3);
         } else {
             // wide kernels: outputs go straight out (a row entry is still an input of later outputs)
             for (int t = lane; t < G; t += 64) {
@@ -435,6 +440,7 @@ __device__ __forceinline__ void kde_finalize(const KdeView& kv, double* row, boo
                 out[t] = normalize ? v : v * scale;
                 tot += v;
             }
+            mk(3);
             if (normalize) {
                 tot = wave_sum(tot);
                 for (int t = lane; t < G; t += 64) out[t] = out[t] / tot;
@@ -447,6 +453,133 @@ __device__ __forceinline__ void kde_finalize(const KdeView& kv, double* row, boo
     if (normalize) {
         tot = wave_sum(tot);
         for (int t = lane; t < G; t += 64) out[t] = row[t] / tot;       // pdf /= pdf.sum()
+    }
+}
+
+// k_hist's finish (fz_hist.h, FZ_HIST_FINISH): kde_finalize<true>(.., bymass = true) with the same operations on the same operands in
+// the same order -- every quotient the IEEE division, every output the sum fma(row[t + h], kr[w2 - h], v) over h = 0 .. w2 from 0.0,
+// the total each lane's outputs lane, lane + 64, .. ascending and then wave_sum -- but issued so that their latencies overlap
+// (docs/k_hist.md, "The finish"):
+//   * the mass division reads normtab and the row for EIGHT trips (QB groups of four) before the first of their divisions
+//     (kde_finalize: a global load, an LDS read and a full wait per trip, twelve times in a row at the headline's shape; all
+//     sixteen trips of the longest row at once cost the headline 14 spilled vector registers);
+//   * the convolution is the blocked form of k_hist's class_flush / pdf_stage_mc: lane L owns outputs NACC L .. NACC L + NACC - 1
+//     and keeps a window of NACC row entries in registers, so that a tap costs ONE LDS read per lane, asked for NACC FMAs before
+//     its first use, and feeds NACC independent chains (kde_finalize: two reads per tap, each waited for in full, in front of a
+//     chain two deep: 612 serial LDS round trips per object at G = 701 and 51 taps);
+//   * the outputs are parked in row[t] (by then no lane reads an input any more: a wave's LDS operations are executed in order) and
+//     come back transposed, lane + 64 j, for the total in kde_finalize's order and the coalesced store; they stay in registers for
+//     the division by the total, whose quotients are independent.
+// Where the two-register tap form does not apply (w2 >= 128) or a lane's block does not cover the grid (G > 64 NACC): kde_finalize.
+// The row has G + w2 entries and NO pad behind them (k_hist's single-width rows: acc_stride = G + 2 w0): the lanes whose block ends
+// past G clamp their reads to the row's last entry and their sums are not used.
+template <int NACC = 12, class MK = NoMark, int QB = 2>
+__device__ __forceinline__ void hist_finish_row(const KdeView& kv, double* row, bool ok, int normalize, double* out, int lane,
+                                                double scale, MK mk = MK{}) {
+    const int G = (int)kv.G, w2 = 2 * kv.w0;
+    if (w2 >= 128 || G > 64 * NACC) { kde_finalize<true>(kv, row, ok, normalize, out, lane, scale, true, mk); return; }
+    if (!ok) { for (int t = lane; t < G; t += 64) out[t] = NAN; return; }
+    constexpr int UG = 4;                                           // trips per group: a group's divisions sit in one basic block
+    constexpr int NQ = (64 * NACC + 126 + 63) / 64;                 // trips of the longest row
+    constexpr int NQG = (NQ + UG - 1) / UG;
+    const int n = G + w2, last = n - 1;
+    mk(1);
+#pragma unroll
+    for (int b = 0; b < NQG; b += QB) {
+        double rv[QB * UG], nv[QB * UG];
+#pragma unroll
+        for (int g = 0; g < QB; ++g) {
+            if (64 * UG * (b + g) < n) {                            // wave-uniform
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+                    const int k = min(lane + 64 * (UG * (b + g) + u), last);
+                    nv[UG * g + u] = kv.normtab[k]; rv[UG * g + u] = row[k];
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < QB; ++g) {
+            if (64 * UG * (b + g) < n) {
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+                    const int k = lane + 64 * (UG * (b + g) + u);
+                    const double q = rv[UG * g + u] / nv[UG * g + u];
+                    if (k < n) row[k] = q;
+                }
+            }
+        }
+    }
+    mk(2);
+    __builtin_amdgcn_wave_barrier();                                // (no instruction: the compiler keeps the row's writes in front of the reads below)
+    const double* kr = kv.kern + kv.koff0;
+    const double ka = (lane <= w2) ? kr[lane] : 0.0;                // w2 + 1 <= 127 taps in two registers across the wave
+    const double kb = (lane + 64 <= w2) ? kr[lane + 64] : 0.0;
+    const int kal = __double2loint(ka), kah = __double2hiint(ka), kbl = __double2loint(kb), kbh = __double2hiint(kb);
+    const int base = NACC * min(lane, (G - 1) / NACC);              // lanes past G repeat the last lane's block (unused sums)
+    const int room = last - base;                                   // the row's last entry, seen from the block
+    const double* r0 = row + base;
+    double acc[NACC], win[NACC];
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) { acc[a] = 0.0; win[a] = r0[min(a, room)]; }
+    for (int h = 0; h <= w2; h += NACC) {
+#pragma unroll
+        for (int u = 0; u < NACC; ++u) {
+            if (h + u <= w2) {                                      // wave-uniform
+                const int q = w2 - (h + u);
+                const double tap = (q < 64) ? __hiloint2double(__builtin_amdgcn_readlane(kah, q), __builtin_amdgcn_readlane(kal, q))
+                                            : __hiloint2double(__builtin_amdgcn_readlane(kbh, q - 64), __builtin_amdgcn_readlane(kbl, q - 64));
+#pragma unroll
+                for (int a = 0; a < NACC; ++a) acc[a] = fma(win[(a + u) % NACC], tap, acc[a]);
+                win[u] = r0[min(NACC + h + u, room)];               // the entry that left the window makes room for the next one
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();                                // every lane's reads, then the parked outputs
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) { if (NACC * lane + a < G) row[NACC * lane + a] = acc[a]; }
+    __builtin_amdgcn_wave_barrier();
+    constexpr int NOG = (NACC + UG - 1) / UG;
+    double val[NOG * UG];
+    double tot = 0.0;
+#pragma unroll
+    for (int g = 0; g < NOG; ++g) {
+        if (64 * UG * g < G) {                                      // wave-uniform
+#pragma unroll
+            for (int u = 0; u < UG; ++u) val[UG * g + u] = row[min(lane + 64 * (UG * g + u), G - 1)];
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < NOG; ++g) {
+        if (64 * UG * g < G) {
+#pragma unroll
+            for (int u = 0; u < UG; ++u) { if (lane + 64 * (UG * g + u) < G) tot += val[UG * g + u]; }      // kde_finalize's order: ascending per lane
+        }
+    }
+    mk(3);
+    if (normalize) {
+        tot = wave_sum(tot);
+#pragma unroll
+        for (int g = 0; g < NOG; ++g) {
+            if (64 * UG * g < G) {
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+                    const int t = lane + 64 * (UG * g + u);
+                    const double v = val[UG * g + u] / tot;         // pdf /= pdf.sum()
+                    if (t < G) out[t] = v;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < NOG; ++g) {
+            if (64 * UG * g < G) {
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+                    const int t = lane + 64 * (UG * g + u);
+                    if (t < G) out[t] = val[UG * g + u] * scale;
+                }
+            }
+        }
     }
 }
 
