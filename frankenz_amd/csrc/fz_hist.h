@@ -94,6 +94,32 @@ namespace fz {
                                  // together (hist_finish_row, fz_kernels.h; docs/k_hist.md, "The finish"): the same operations on the same operands
                                  // in the same order as kde_finalize, which every other kernel keeps.  0: the code without it
 #endif
+// The switches below are for what the finish does in front of the PDF row (docs/k_hist.md, "In front of the PDF row"); none changes an
+// operation, an operand or an order of additions.  FZ_HIST_BAND_ACQ is what the measured split of that part asked for and is on; the
+// others were built, measured and are compiled out (their figures are in the document).
+#ifndef FZ_HIST_BAND_ACQ
+#define FZ_HIST_BAND_ACQ 1       // the acquire in front of the ambiguous band's loads has WORKGROUP scope: the entries were written by lanes of this very
+                                 // wave, and a CU's vector L1 is coherent for the waves of a workgroup, so nothing has to be invalidated.  The agent-scope
+                                 // acquire (0) empties the CU's vector L1 once per object and wave -- under the other fifteen waves' table gathers
+#endif
+#ifndef FZ_HIST_BAND
+#define FZ_HIST_BAND 0           // 1: the ambiguous band takes FZ_HIST_BAND_T entries per lane and trip -- their loads first, then the table gathers of each
+                                 // stage, then the arithmetic as independent chains, the histogram adds in the list's order -- and (FZ_HIST_BAND_EARLY)
+                                 // the first trip's loads go out in front of the reductions.  Every T > 1 spills vector registers in the headline
+#endif
+#ifndef FZ_HIST_BAND_T
+#define FZ_HIST_BAND_T 4
+#endif
+#ifndef FZ_HIST_BAND_EARLY
+#define FZ_HIST_BAND_EARLY 1
+#endif
+#ifndef FZ_HIST_RED3
+#define FZ_HIST_RED3 0           // 1: the finish's three wave reductions advance together, a step of each per LDS round trip (hist_reduce3), and its
+                                 // two logarithms gather together (log_pos_pair).  That part is under 0.3 % of a wave's life; nothing gained when timed
+#endif
+#ifndef FZ_HIST_NACC
+#define FZ_HIST_NACC 12          // outputs per lane of hist_finish_row's convolution.  11 (no bank conflict on the window reads) was not faster, 13 spills
+#endif
 #ifndef FZ_HIST_PRIO
 #define FZ_HIST_PRIO 1           // > 0: the headline's waves change their issue priority (s_setprio) with their progress through the interval between
                                  // two tile barriers, so that a SIMD's four waves arrive there together (docs/k_hist.md, "Waves of a SIMD kept in
@@ -131,36 +157,43 @@ __device__ __forceinline__ void hist_setprio(int p) {
 // the prologue up to the first barrier, and its whole life -- and adds them at the end to its wave index's row of this table, which the launcher
 // has printed and cleared per launch (hist_wstats_print below).  The last four words count the SIMD the wave ran on (HW_ID), to check which waves share one.
 #ifdef FZ_HIST_WSTATS
-static __device__ unsigned long long fz_hwstats[16 * 16];
+static __device__ unsigned long long fz_hwstats[16 * 32];      // 32 words per wave index
 #define FZ_HIST_WSTATS_ON 1
 // where the waves waited: per wave index the share of its life at the tile barrier (a), at the round's two __syncthreads() (b), in
 // the finish (c) and in the prologue (d); one line per age rank (wave >> 2), four waves (SIMDs) each.  Waits for the launch on
 // `stream`, prints the table and clears it
 inline void hist_wstats_print(hipStream_t stream, int nb, long long n, long long M, long long blocks, int nw) {
-    unsigned long long h[16 * 16], z[16 * 16] = {0};
+    unsigned long long h[16 * 32], z[16 * 32] = {0};
     (void)hipStreamSynchronize(stream);
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(fz_hwstats), sizeof h);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(fz_hwstats), z, sizeof z);
     fprintf(stderr, "HWSTATS k_hist<%d bands>: n %lld M %lld, %lld blocks x %d waves\n", nb, n, M, blocks, nw);
     for (int r = 0; r < nw / 4; ++r) {
-        double s[5] = {0, 0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        double s[5] = {0, 0, 0, 0, 0}, c[4] = {0, 0, 0, 0}, f[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         char simd[128]; int q = 0;
         for (int w = 4 * r; w < 4 * r + 4; ++w) {
-            const unsigned long long* e = h + w * 16;
+            const unsigned long long* e = h + w * 32;
             for (int k = 0; k < 5; ++k) s[k] += (double)e[k];
             for (int k = 0; k < 4; ++k) c[k] += (double)e[12 + k];
+            for (int k = 0; k < 8; ++k) f[k] += (double)e[16 + k];
             q += snprintf(simd + q, sizeof simd - q, " w%d:%llu/%llu/%llu/%llu", w, e[8], e[9], e[10], e[11]);
         }
         const double life = s[4] > 0 ? s[4] : 1.0;
         fprintf(stderr, "HWSTATS rank %d (waves %d-%d): life %.4g cycles per wave | tile barrier %.2f %% | round barriers %.2f %% | finish %.2f %% | "
-                        "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 16 + 5] ? h[4 * r * 16 + 5] : 1)),
+                        "prologue %.2f %% | per wave, tile barrier %%:", r, 4 * r, 4 * r + 3, s[4] / (4.0 * (double)(h[4 * r * 32 + 5] ? h[4 * r * 32 + 5] : 1)),
                 100 * s[0] / life, 100 * s[1] / life, 100 * s[2] / life, 100 * s[3] / life);
-        for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 16] / (double)(h[w * 16 + 4] ? h[w * 16 + 4] : 1));
+        for (int w = 4 * r; w < 4 * r + 4; ++w) fprintf(stderr, " %.2f", 100.0 * (double)h[w * 32] / (double)(h[w * 32 + 4] ? h[w * 32 + 4] : 1));
         fprintf(stderr, " | launches on SIMD 0/1/2/3:%s\n", simd);
         // the finish by its parts: c1 last drains, reductions, logarithms, ambiguous band, ln-max / ln-evidence; c2 the division by the kernel
         // mass; c3 the convolution and the parked outputs; c4 the total, the normalisation and the stores
         fprintf(stderr, "HWSTATS rank %d finish: c1 %.2f %% | c2 %.2f %% | c3 %.2f %% | c4 %.2f %% of the waves' life\n", r,
-                100 * c[0] / life, 100 * c[1] / life, 100 * c[2] / life, 100 * c[3] / life);
+                100 * (c[0] + f[0] + f[1] + f[2] + f[7]) / life, 100 * c[1] / life, 100 * c[2] / life, 100 * c[3] / life);
+        // c1 by its parts: c1a the last drains; c1b the reductions, the logarithms and `ok` (with FZ_HIST_BAND also the band's fences and the
+        // issue of its first loads); c1c the ambiguous band; c1d ln-max, ln-evidence, the redo append and the row routine's entry
+        const double nobj = f[6] < 1 ? 1 : f[6];
+        fprintf(stderr, "HWSTATS rank %d in front of the row: c1a %.2f %% | c1b %.2f %% | c1c %.2f %% (its fences, where the band has them: %.2f %%) | c1d %.2f %% "
+                        "of the waves' life | per object: %.1f ambiguous entries, %.2f band trips, %.3f objects with a list\n", r, 100 * f[0] / life,
+                100 * f[1] / life, 100 * (f[2] + f[7]) / life, 100 * f[7] / life, 100 * c[0] / life, f[3] / nobj, f[4] / nobj, f[5] / nobj);
     }
 }
 #else
@@ -363,6 +396,42 @@ __device__ __forceinline__ double wave_max_pos_hi(double v) {
     return __hiloint2double(mx(mx(a, b), mx(c, d)), 0);
 }
 
+// The finish's three reductions -- wave_max(a), wave_sum(s), wave_maxf(t) -- a step of each per trip: the exchanges of a step are issued
+// together and waited for once, six LDS round trips instead of eighteen.  Every lane computes what the three routines compute: the same
+// partner (lane ^ o), the same combine, o = 32, 16, .. 1 in that order (the sum is not associative: its tree is wave_sum's).
+__device__ __forceinline__ void hist_reduce3(double& a, double& s, float& t) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double xa = __shfl_xor(a, o, 64), xs = __shfl_xor(s, o, 64);
+        const float xt = __shfl_xor(t, o, 64);
+        a = fmax(a, xa); s += xs; t = fmaxf(t, xt);
+    }
+}
+// log_pos(x1, tb) and log_pos(x2, tb) with the two table reads issued together: log_pos_t<false>'s operations per value, the rare
+// fix-up of both behind one wave-uniform branch
+__device__ __forceinline__ void log_pos_pair(double x1, double x2, const FastTabs& tb, double& l1, double& l2) {
+    auto head = [&](double x, double& mant, int& ex) -> double2 {
+        mant = __builtin_amdgcn_frexp_mant(x); ex = __builtin_amdgcn_frexp_exp(x);
+        return tb.logt[((unsigned)__double2hiint(mant) >> 13) & 127u];
+    };
+    auto tail = [](double mant, int ex, double2 t) {
+        const double r = fma(mant, t.x, -1.0), r2 = r * r;
+        const double q01 = fma(r, 1.0 / 3.0, -0.5), q23 = fma(r, 0.2, -0.25);
+        const double q = fma(r2, fma(r2, -1.0 / 6.0, q23), q01);
+        const double p = fma(r2, q, r);
+        return fma((double)ex, 0.6931471805599453, t.y) + p;
+    };
+    double m1, m2; int e1, e2;
+    const double2 t1 = head(x1, m1, e1), t2 = head(x2, m2, e2);
+    l1 = tail(m1, e1, t1); l2 = tail(m2, e2, t2);
+    const bool ok1 = __builtin_amdgcn_class(x1, 0x180), ok2 = __builtin_amdgcn_class(x2, 0x180);
+    if (__ballot(!(ok1 && ok2)) != 0ull) {
+        asm volatile("" ::: "memory");
+        if (!ok1) l1 = (x1 == 0.0) ? -INFINITY : ((x1 == INFINITY) ? INFINITY : NAN);
+        if (!ok2) l2 = (x2 == 0.0) ? -INFINITY : ((x2 == INFINITY) ? INFINITY : NAN);
+    }
+}
+
 // chi2 of the band-constant-variance algebra in two instructions per band (k_hist, below); 0 restores the exact-difference form
 #ifndef FZ_HIST_CHI2_2OP
 #define FZ_HIST_CHI2_2OP 1
@@ -450,7 +519,8 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     auto wclk = [&]() -> unsigned long long { if constexpr (WST) return __builtin_readcyclecounter(); else return 0ull; };
     [[maybe_unused]] const unsigned long long wst_life = wclk();
     // (c) by its parts: wmark(k) closes part k of the finish (1 .. 4, hist_wstats_print names them)
-    [[maybe_unused]] unsigned long long wst_cp[4] = {0, 0, 0, 0}, wst_last = 0;
+    // (5 .. 7 close c1a .. c1c, the parts of what stands in front of the PDF row; 1 then closes the rest of it, c1d)
+    [[maybe_unused]] unsigned long long wst_cp[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wst_last = 0, wst_ne = 0, wst_nt = 0, wst_nl = 0, wst_no = 0;
     [[maybe_unused]] auto wmark = [&](int k) {
         if constexpr (WST) { const unsigned long long now = wclk(); wst_cp[k - 1] += now - wst_last; wst_last = now; }
     };
@@ -459,6 +529,12 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
     // gained nothing; per-model errors, per-object band counts and the segmented kernels spill more vector registers with it, as does
     // the direct form at 6 bands; 7 and 8 bands were not tabulated (docs/k_hist.md, "The finish", has the table): they keep the parent's call
     constexpr bool FIN = (FZ_HIST_FINISH == 1) && !SEG && !OBJK && SRC::LMODE == 1 && SRC::NB <= 5;
+    // FZ_HIST_BAND_ACQ: the same forms (docs/k_hist.md, "In front of the PDF row"; every other form keeps the agent-scope acquire).  The three
+    // that are compiled out -- FZ_HIST_BAND / FZ_HIST_RED3 / FZ_HIST_NACC -- are for the screen forms among them
+    constexpr bool ACQW = (FZ_HIST_BAND_ACQ == 1) && FIN;
+    constexpr bool BAND = (FZ_HIST_BAND == 1) && FIN && !EXACT;
+    constexpr bool RED3 = (FZ_HIST_RED3 == 1) && FIN && !EXACT;
+    constexpr int BNT = FZ_HIST_BAND_T, FNACC = (FIN && !EXACT) ? FZ_HIST_NACC : 12;
     static_assert(!OBJK || TW == 1, "per-object band counts: one object per wave");
     static_assert(!SEG || (OBJK && SRC::NB <= 8), "segments: run-time band counts, 4-8 bands");
     constexpr double SEG_VBIG = BT <= 5 ? 0x1p192 : (BT == 6 ? 0x1p160 : (BT == 7 ? 0x1p137 : 0x1p120));      // 2^(960 / BT): BT such terms multiply without overflow
@@ -1263,27 +1339,92 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                 if constexpr (SEAM) asm volatile("" : "+v"(lanef));
                 if constexpr (!EXACT) {
                     while (hs.pend[o] > 0) drain(o, std::integral_constant<bool, SEG>{}, lanef);
-                } else {
-                    wbest_run = wave_max(hs.Sc[o]);
+                }
+                wmark(5);
+                // the ambiguous list is final here.  FZ_HIST_BAND: its fences and the first trip's loads go out now, so that their round trip
+                // runs under the reductions and logarithms below.  Entry `u` of a lane in the trip at c0 is c0 + 64 u + lane.
+                // (band_acquire: the acquire in front of the list's loads, FZ_HIST_BAND_ACQ)
+                const Cand* const cb = ambw + (size_t)o * cap;
+                auto band_acquire = [&]() {
+                    if constexpr (ACQW) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                };
+                [[maybe_unused]] Cand be[BAND ? BNT : 1];
+                [[maybe_unused]] auto band_load = [&](int c0, int nn) {
+#pragma unroll
+                    for (int u = 0; u < BNT; ++u) { const int k = c0 + 64 * u + lane; be[u] = cb[k < nn ? k : 0]; }
+                };
+                if constexpr (BAND) {
+                    const int na0 = (FZ_HIST_BAND_EARLY == 1) ? __builtin_amdgcn_readfirstlane(hs.namb[o]) : 0;
+                    if (na0 > 0) {
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // entries were written by other lanes of this wave
+                        band_acquire();
+                        band_load(0, na0);
+                    }
                 }
                 // ln L of the best model = ln L(mode) + ln of its exact relative weight (4e-16 relative on the weight: 1e-16 on ln-max)
-                if constexpr (!EXACT) wbest_run = wave_max(hs.wmx[o]);
-                const double lbest = (wbest_run > 0.0) ? uniform_d(lrf + log_pos(wbest_run, tb)) : -INFINITY;
-                const double stot = wave_sum(EXACT ? hs.S[o] : hs.Sc[o]);
-                const double le = lrf + log_pos(stot, tb);
-                const float tm = EXACT ? 0.f : wave_maxf(hs.tmax[o]);
+                double lbest, stot, le;
+                float tm;
+                if constexpr (RED3) {
+                    // (the parent's three reductions and two logarithms: a step of each per LDS round trip, the two table reads together)
+                    wbest_run = hs.wmx[o]; stot = hs.Sc[o]; tm = hs.tmax[o];
+                    hist_reduce3(wbest_run, stot, tm);
+                    double l1, l2;
+                    log_pos_pair(wbest_run, stot, tb, l1, l2);
+                    lbest = (wbest_run > 0.0) ? uniform_d(lrf + l1) : -INFINITY;
+                    le = lrf + l2;
+                } else {
+                    if constexpr (EXACT) wbest_run = wave_max(hs.Sc[o]);
+                    else wbest_run = wave_max(hs.wmx[o]);
+                    lbest = (wbest_run > 0.0) ? uniform_d(lrf + log_pos(wbest_run, tb)) : -INFINITY;
+                    stot = wave_sum(EXACT ? hs.S[o] : hs.Sc[o]);
+                    le = lrf + log_pos(stot, tb);
+                    tm = EXACT ? 0.f : wave_maxf(hs.tmax[o]);
+                }
                 // no candidate at all, an evidence that is not a number, or a best weight so far below the mode that weights relative to
                 // the MODE leave the comfortable range (2^-400: every pair within the drop bar of it is still a normal number well above
                 // the exponential's clamp, and chi2 stays small enough -- < ~600 -- for the classifier's error bound): the exact ln-space sweep decides
                 const bool ok = (le - le == 0.0) && (lbest > -INFINITY) && (EXACT ? (wbest_run > 1e-24) : (tm >= -400.f)) && hs.namb[o] >= 0 && kok;
                 if constexpr (SEG) { if (mcw && segcur >= 0) class_flush(kv.seg_rank[segcur], row, pdfs + i * kv.G); }      // the last class
-                // the ambiguous band, by the reference's own rule (pdf.py:591) with the exact maximum and evidence
+                wmark(6);
                 const int na = __builtin_amdgcn_readfirstlane(hs.namb[o]);
+                if constexpr (WST) { wst_no += 1; if (na > 0) { wst_ne += (unsigned)na; wst_nl += 1; wst_nt += (unsigned)((na + 64 * (BAND ? BNT : 1) - 1) / (64 * (BAND ? BNT : 1))); } }
+                // the ambiguous band, by the reference's own rule (pdf.py:591) with the exact maximum and evidence
+                if constexpr (BAND) {
+                    if (na > 0) {
+                        if constexpr (FZ_HIST_BAND_EARLY != 1) {
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                            band_acquire();
+                            band_load(0, na);
+                        }
+                        const double thr = wt_thresh * exp_neg(lbest - le, tb);     // wt_thresh * max(wt)
+                        for (int c0 = 0;;) {
+                            // the trip's table reads stage by stage (ln-like, weight, share of the evidence), BNT independent chains in one basic
+                            // block; then the histogram adds for u = 0, 1, ..: every LDS atomic carries the 64 entries of one trip of the
+                            // one-entry loop, in that loop's sequence, so every bin's sum is that loop's bit for bit
+                            bool in[BNT], st[BNT];
+                            double l[BNT], w[BNT], x[BNT];
+#pragma unroll
+                            for (int u = 0; u < BNT; ++u) { in[u] = c0 + 64 * u + lane < na; l[u] = lnl_fin(be[u].lnl); }
+#pragma unroll
+                            for (int u = 0; u < BNT; ++u) w[u] = exactw_tab(be[u].lnl, tb, std::false_type{});
+#pragma unroll
+                            for (int u = 0; u < BNT; ++u) x[u] = exp_neg((in[u] ? l[u] : -INFINITY) - le, tb);
+#pragma unroll
+                            for (int u = 0; u < BNT; ++u) st[u] = in[u] && (x[u] > thr);   // strict
+#pragma unroll
+                            for (int u = 0; u < BNT; ++u) { if (st[u]) unsafeAtomicAdd(&row[be[u].j + w0], w[u]); }
+                            c0 += 64 * BNT;
+                            if (c0 >= na) break;
+                            band_load(c0, na);
+                        }
+                    }
+                } else
                 if (na > 0) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // entries were written by other lanes of this wave
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    band_acquire();
+                    wmark(8);
                     const double thr = wt_thresh * exp_neg(lbest - le, tb);     // wt_thresh * max(wt)
-                    const Cand* cb = ambw + (size_t)o * cap;
                     for (int c0 = 0; c0 < na; c0 += 64) {
                         const int k = c0 + lane;
                         const bool in1 = k < na;
@@ -1318,6 +1459,7 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                         if (s1) unsafeAtomicAdd(&row[e1.j + w0], w1);
                     }
                 }
+                wmark(7);
                 if (lane == 0) {
                     if (hf.lmap) hf.lmap[i] = lbest;
                     if (hf.levid) hf.levid[i] = le;
@@ -1339,10 +1481,10 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
                     }
                 }
                 if constexpr (WST) {
-                    if constexpr (FIN) hist_finish_row<12>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, wmark);
+                    if constexpr (FIN) hist_finish_row<FNACC>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, wmark);
                     else kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true, wmark);
                     wmark(4);
-                } else if constexpr (FIN) hist_finish_row<12>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0);
+                } else if constexpr (FIN) hist_finish_row<FNACC>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0);
                 else kde_finalize<true>(kvf, row, ok, hf.normalize, pdfs + i * kvf.G, lanef, ok ? 1.0 / stot : 1.0, true);
             }
         }
@@ -1358,11 +1500,13 @@ __global__ __launch_bounds__(NW * 64) void k_hist(HistArgs<SRC> a_, const KdeVie
         const unsigned long long life = wclk() - wst_life;
         const int simd = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);      // HW_ID bits 5:4
         if (lane == 0 && wave < 16) {
-            unsigned long long* h = fz_hwstats + wave * 16;
+            unsigned long long* h = fz_hwstats + wave * 32;
             atomicAdd(h + 0, wst_a); atomicAdd(h + 1, wst_b); atomicAdd(h + 2, wst_c); atomicAdd(h + 3, wst_d);
             atomicAdd(h + 4, life); atomicAdd(h + 5, 1ull); atomicAdd(h + 6, (unsigned long long)nrounds);
             atomicAdd(h + 8 + (simd & 3), 1ull);
             for (int k = 0; k < 4; ++k) atomicAdd(h + 12 + k, wst_cp[k]);
+            for (int k = 0; k < 3; ++k) atomicAdd(h + 16 + k, wst_cp[4 + k]);
+            atomicAdd(h + 19, wst_ne); atomicAdd(h + 20, wst_nt); atomicAdd(h + 21, wst_nl); atomicAdd(h + 22, wst_no); atomicAdd(h + 23, wst_cp[7]);
         }
 #endif
     }
