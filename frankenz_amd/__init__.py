@@ -7,7 +7,7 @@ All arithmetic of the path runs in hand-written HIP kernels reached through the
 C ABI in ``include/frankenz_hip.h`` (``libfrankenz_hip.so``, loaded with ctypes).
 There is no CPU fallback: importing the engine without the built library raises.
 """
-from .pdf import (PDFDict, gaussian, gauss_kde, gauss_kde_dict, loglike, logprob, logprob_prior,
+from .pdf import (PDFDict, gaussian, gaussian_bin, gauss_kde, gauss_kde_dict, loglike, logprob, logprob_prior,
                   logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize, sample_labels)
 from .bruteforce import BruteForce
 from .knn import NearestNeighbors
@@ -16,6 +16,6 @@ from .sparse import SparseFits
 from . import calibrate, fitting, networks, pdf, plotting, priors, reddening, samplers, simulate
 
 __version__ = "0.1.0"
-__all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gauss_kde",
+__all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gaussian_bin", "gauss_kde",
            "gauss_kde_dict", "loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "luptitude", "magnitude",
            "pdfs_resample", "pdfs_summarize", "sample_labels", "model_weight_sampler", "model_weight_em", "SparseFits", "calibrate", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]

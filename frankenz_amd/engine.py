@@ -409,6 +409,24 @@ class Engine(object):
                                       ptr(value_errs), ptr(value_mask), ptr(mean), ptr(var), ptr(share), ptr(ns)))
         return int(ns[0])
 
+    # -- posterior bin masses and mixture CDFs (docs/bins.md; fz_bins.h) ----
+    def row_bins(self, rows, n, W, M, labels, label_errs, edges, E, p, lncut=-np.inf, normalize=True, below=None, above=None,
+                 neighbors=None, nnbr=None):
+        """fz_row_bins: rows (n, W) of ln-weights over Gaussian labels (M) -> the masses ``p`` (n, E - 1) of the bins between the ``E``
+        edges [, ``below``, ``above`` (n)]; ``lncut`` = ln(wt_thresh) (-inf: none); returns the number of rows without a posterior"""
+        ns = np.zeros(1, dtype=np.int64)
+        check(self.lib.fz_row_bins(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(labels), ptr(label_errs),
+                                   ptr(edges), int(E), float(lncut), int(bool(normalize)), ptr(p), ptr(below), ptr(above), ptr(ns)))
+        return int(ns[0])
+
+    def row_cdf(self, rows, n, W, M, labels, label_errs, points, P, cdf, per_object=False, lncut=-np.inf, neighbors=None, nnbr=None):
+        """fz_row_cdf: the mixture CDF of every row at ``points`` (P) or, with ``per_object``, (n, P) -> ``cdf`` (n, P); returns the
+        number of rows without a posterior"""
+        ns = np.zeros(1, dtype=np.int64)
+        check(self.lib.fz_row_cdf(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(labels), ptr(label_errs),
+                                  ptr(points), int(P), int(bool(per_object)), float(lncut), ptr(cdf), ptr(ns)))
+        return int(ns[0])
+
     def phot_sums(self, x, xe, xm, mean, var, n, B, clip=0.):
         """fz_phot_sums -> (sums (3, B) float64 = A, B, C; counts (2, B) int64 = n, nclip)"""
         sums, counts = np.zeros((3, int(B))), np.zeros((2, int(B)), dtype=np.int64)

@@ -17,7 +17,10 @@ import numpy as np
 from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
-           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt", "posterior_moments"]
+           "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt", "posterior_moments",
+           "gaussian_bin", "posterior_bins", "posterior_cdf", "BINS_MAX"]
+
+BINS_MAX = 256       # FZ_BINS_MAX: bins of a posterior_bins call, points of a posterior_cdf call
 
 
 def _ndim_dtype(data_mask, models_mask):
@@ -297,6 +300,101 @@ def gaussian(mu, std, x):
     dictionary tables."""
     d = (np.asarray(x) - mu) / std
     return np.exp(-0.5 * np.square(d)) / (math.sqrt(2.0 * math.pi) * std)
+
+
+def gaussian_bin(mu, std, bins):
+    """N(mu, std) integrated over the bins with edges ``bins`` (pdf.py:428-441): the ``len(bins) - 1`` differences of the CDF
+    ``0.5 (1 + erf)`` at the edges -- host helper, the reference's arithmetic."""
+    from scipy.special import erf
+    dif = bins - mu
+    y = dif / (np.sqrt(2) * std)
+    cdf = 0.5 * (1. + erf(y))
+    return cdf[1:] - cdf[:-1]
+
+
+def _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh):
+    """the arguments `posterior_bins` and `posterior_cdf` share, checked before any device call
+    -> lw, y, s, nb, nn, N, W, M, lncut"""
+    if (neighbors is None) != (Nneighbors is None):
+        raise ValueError("`neighbors` and `Nneighbors` come together")
+    lw = _rows_arg(logwt, np.float64, "logwt")
+    y, s = _rows_arg(labels, np.float64, "labels"), _rows_arg(label_errs, np.float64, "label_errs")
+    if len(lw.shape) != 2 or len(y.shape) != 1 or tuple(s.shape) != tuple(y.shape):
+        raise ValueError("`logwt` must be (Ndata, W), `labels` and `label_errs` (Nmodel,)")
+    N, W = (int(v) for v in lw.shape)
+    M = int(y.shape[0])
+    nb, nn = _rows_arg(neighbors, np.int64, "neighbors"), _rows_arg(Nneighbors, np.int64, "Nneighbors")
+    if nb is not None and (tuple(nb.shape) != (N, W) or tuple(nn.shape) != (N,)):
+        raise ValueError("`neighbors` must have the shape of `logwt` and `Nneighbors` one entry per object")
+    if nb is None and W != M:
+        raise ValueError("dense rows have one entry per model: %d entries, %d models" % (W, M))
+    if W < 1 or M < 1:
+        raise ValueError("rows of %d entries over %d models" % (W, M))
+    wt = 0. if wt_thresh is None else float(wt_thresh)
+    if not (0. <= wt < 1.):
+        raise ValueError("`wt_thresh` must lie in [0, 1) (got %r)" % (wt_thresh,))
+    return lw, y, s, nb, nn, N, W, M, (np.log(wt) if wt > 0. else -np.inf)
+
+
+def posterior_bins(logwt, labels, label_errs, bins, neighbors=None, Nneighbors=None, wt_thresh=1e-3, normalize=True,
+                   return_outside=False, out=None, device=None):
+    """Probability per bin, P(e_k <= label < e_k+1 | data), of a Gaussian label kernel under rows of ln-weights (extension;
+    docs/bins.md states the law): per row the entries with ``wt > wt_thresh * max(wt)`` (decided in ln space; 0 or None: every entry
+    with a positive weight), each model's ``N(labels[j], label_errs[j])`` integrated exactly between the edges ``bins`` -- a
+    difference of two error functions, no grid.  ``label_errs == 0`` is a point mass.
+
+    ``logwt`` ``(Ndata, W)`` with ``neighbors`` / ``Nneighbors`` as in ``posterior_moments`` (without them dense rows,
+    ``W == Nmodel``); ``bins`` the ``Nbins + 1 <= 257`` finite, strictly increasing edges.  Every array is NumPy or a device array.
+    ``normalize`` divides each row by its sum over the bins (conditional on the range: what ``samplers.population_sampler`` and
+    ``hierarchical_sampler`` take; nan when no mass lies inside).  Returns ``(Ndata, Nbins)``, with ``return_outside`` also the
+    masses ``(below, above)`` of the range.  ``out``: a C-contiguous float64 ``(Ndata, Nbins)`` NumPy or device array, filled in
+    place and returned.  A row without a posterior gives nan."""
+    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+    e = _rows_arg(bins, np.float64, "bins")
+    if len(e.shape) != 1 or int(e.shape[0]) < 2:
+        raise ValueError("`bins` must be a 1-D array of at least 2 edges")
+    E = int(e.shape[0])
+    if E - 1 > BINS_MAX:
+        raise NotImplementedError("%d bins, the limit is %d (FZ_BINS_MAX)" % (E - 1, BINS_MAX))
+    if isinstance(e, np.ndarray) and not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
+        raise ValueError("`bins` must be finite and strictly increasing")
+    if out is None:
+        out = np.full((N, E - 1), np.nan)
+    elif tuple(out.shape) != (N, E - 1) or _rows_arg(out, np.float64, "out") is not out:
+        raise ValueError("`out` must be a C-contiguous float64 array of shape (Ndata, Nbins) = (%d, %d)" % (N, E - 1))
+    below, above = (np.full(N, np.nan), np.full(N, np.nan)) if return_outside else (None, None)
+    get_engine(device).row_bins(lw, N, W, M, y, s, e, E, out, lncut=lncut, normalize=normalize, below=below, above=above,
+                                neighbors=nb, nnbr=nn)
+    return (out, (below, above)) if return_outside else out
+
+
+def posterior_cdf(logwt, labels, label_errs, points, neighbors=None, Nneighbors=None, wt_thresh=1e-3, device=None):
+    """The mixture CDF P(label <= x | data) of the same kernel, selection and normalisation as ``posterior_bins`` (extension;
+    docs/bins.md).  ``points``: ``(Ndata, P)`` per object, ``(1, P)`` or ``(P,)`` shared by all objects -- ``P <= 256``, finite, in
+    any order -- giving ``(Ndata, P)``; or ``(Ndata,)``, one point per object, giving ``(Ndata,)``: with the true labels of a
+    validation sample that is its PIT.  (A 1-D array of exactly ``Ndata`` points is read as one per object; pass ``(1, P)`` to share
+    it.)"""
+    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+    x = _rows_arg(points, np.float64, "points")
+    shape = tuple(int(v) for v in x.shape)
+    pit = len(shape) == 1 and shape[0] == N
+    if pit:
+        P, per_object = 1, True
+    elif len(shape) == 1 or (len(shape) == 2 and shape[0] == 1 and N != 1):
+        P, per_object = shape[-1], False
+    elif len(shape) == 2 and shape[0] == N:
+        P, per_object = shape[1], True
+    else:
+        raise ValueError("`points` must be (Ndata, P), (1, P), (P,) or (Ndata,); got %s for %d objects" % (shape, N))
+    if P < 1:
+        raise ValueError("`points` is empty")
+    if P > BINS_MAX:
+        raise NotImplementedError("%d points, the limit is %d (FZ_BINS_MAX)" % (P, BINS_MAX))
+    if isinstance(x, np.ndarray) and not np.isfinite(x).all():
+        raise ValueError("`points` must be finite")
+    cdf = np.full((N, P), np.nan)
+    get_engine(device).row_cdf(lw, N, W, M, y, s, x, P, cdf, per_object=per_object, lncut=lncut, neighbors=nb, nnbr=nn)
+    return cdf[:, 0] if pit else cdf
 
 
 class PDFDict(object):

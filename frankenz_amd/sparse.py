@@ -126,6 +126,27 @@ class SparseFits(object):
         return posterior_moments(self._rows(logwt), values, value_errs, value_mask, scale=self.fit_scale if use_scale else None,
                                  neighbors=self.neighbors, Nneighbors=self.Nneighbors, device=self._device)
 
+    def predict_bins(self, model_labels, model_label_errs, label_bins, logwt=None, wt_thresh=1e-3, normalize=True, return_outside=False,
+                     out=None):
+        """Extension (docs/bins.md): probability per bin of ``label_bins`` (the edges) from the sparse rows, each model a Gaussian
+        ``N(model_labels, model_label_errs)`` integrated exactly between the edges (``pdf.posterior_bins``): the ``(Ndata, Nbins)``
+        stack ``samplers.population_sampler`` and ``hierarchical_sampler`` take, without a grid."""
+        from .pdf import posterior_bins
+        if len(model_labels) != self.NMODEL:
+            raise ValueError("%d labels for %d models" % (len(model_labels), self.NMODEL))
+        return posterior_bins(self._rows(logwt), model_labels, model_label_errs, label_bins, neighbors=self.neighbors,
+                              Nneighbors=self.Nneighbors, wt_thresh=wt_thresh, normalize=normalize, return_outside=return_outside, out=out,
+                              device=self._device)
+
+    def predict_cdf(self, model_labels, model_label_errs, points, logwt=None, wt_thresh=1e-3):
+        """Extension (docs/bins.md): the mixture CDF of the same kernel at ``points`` (``pdf.posterior_cdf``); one point per object,
+        ``(Ndata,)``, is the PIT of a validation sample."""
+        from .pdf import posterior_cdf
+        if len(model_labels) != self.NMODEL:
+            raise ValueError("%d labels for %d models" % (len(model_labels), self.NMODEL))
+        return posterior_cdf(self._rows(logwt), model_labels, model_label_errs, points, neighbors=self.neighbors,
+                             Nneighbors=self.Nneighbors, wt_thresh=wt_thresh, device=self._device)
+
     def predict_phot(self, models, models_err, models_mask, logwt=None):
         """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
         mean and variance of ``scale * model flux`` per band under the rows, the model errors added as the law of total variance,

@@ -624,6 +624,39 @@ int  fz_row_moments(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const
 int  fz_phot_sums(fz_ctx* ctx, const double* x, const double* xe, const double* xm, const double* mean, const double* var, int64_t N,
                   int32_t B, double clip, double* sums, int64_t* counts);
 
+/* ---- posterior bin masses and mixture CDFs of a Gaussian label kernel (extension, no reference counterpart; docs/bins.md) ----
+ * The law.  A row r[0..n) of ln-weights with model indices j_t (dense rows: j_t = t, n = M), labels y (M) and label errors s (M),
+ * edges e[0..E) finite and strictly increasing (E - 1 >= 1 bins), a cut lncut = ln(wt_thresh) < 0 (-inf: none).  A nan among the
+ * counted entries, or a max m that is not finite (n = 0 included), means the row has no posterior (the rule of fz_row_moments): every
+ * output of the row is nan and it is counted in nskip.  Otherwise entry t is included iff r_t - m > lncut (one IEEE subtraction,
+ * strict) and w_t = exp(r_t - m) > 0; Z = sum w_t over the included entries; q_j = 1 / (s_j sqrt 2), each operation rounded once, and
+ *     F_t(x) = 0.5 erfc(-((x - y_j) q_j))               s_j > 0
+ *     F_t(x) = 1 if x >= y_j else 0                     s_j == 0 (q_j = +inf); a bin EDGE at y_j belongs to the bin above it: the
+ *                                                       whole mass goes to the bin with e_k <= y_j < e_k+1, y_j == e[E-1] is above
+ *     p_k   = sum w_t (F_t(e_k+1) - F_t(e_k)) / Z       below = sum w_t F_t(e_0) / Z
+ *     above = sum w_t 0.5 erfc(+((e_E-1 - y_j) q_j)) / Z                  (s_j == 0: 1 if y_j >= e_E-1 else 0)
+ *     normalize: p_k /= sum_k p_k  (nan by IEEE division when no mass lies inside the range)
+ *     C_p   = sum w_t F_t(x_p) / Z                      the CDF at points x (P), shared or per object, in any order
+ * Entries past nnbr[i] are never read.  Every sum is formed in one fixed order that depends on the row length and the bin count alone
+ * (thread q of the object's 64 or 256 adds the entries q, q + 64 [256], ... in order; one xor butterfly over the lanes; the wave sums
+ * in wave order; the sum over bins by lane l over bins l, l + 64, ... and one butterfly): the same bits whatever the chunking under
+ * the workspace limit, the object order, the number of objects in the call, and host or device arguments.
+ * Refusals, before any row is walked: E < 2 (P < 1), an edge or point that is not finite, edges that do not increase strictly, a label
+ * that is not finite or an error that is negative or nan (the smallest such model is named), lncut >= 0 or nan: -4; more than 256
+ * bins or points (FZ_BINS_MAX), W > 2^20 (FZ_DRAW_LMAX) or M >= 2^31: -5.  An index outside [0, M) within the count, or a count outside
+ * [0, W]: -3, before anything is gathered for that row.
+ *
+ * fz_row_bins -- rows (N, W), neighbors (N, W) int64 and nnbr (N) int64 (both NULL: dense rows), p (N, E - 1), below and above (N) or
+ *   NULL: host or device, staged in chunks from the workspace limit.  labels, label_errs (M), edges (E): host or device.  nskip: one
+ *   int64.
+ * fz_row_cdf -- points (P) with per_object == 0, else (N, P) staged with the rows; cdf (N, P). */
+int  fz_row_bins(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                 const double* labels, const double* label_errs, const double* edges, int64_t E, double lncut, int32_t normalize,
+                 double* p, double* below, double* above, int64_t* nskip);
+int  fz_row_cdf(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                const double* labels, const double* label_errs, const double* points, int64_t P, int32_t per_object, double lncut,
+                double* cdf, int64_t* nskip);
+
 /* ---- Monte-Carlo draws of the k-NN fitter on the device (extension; docs/knn.md, knn.py:158-188 / 830-832) ----
  * The reference draws its K feature sets (knn.py:158-188) and every object's query features (knn.py:830-832) with NumPy's normal and
  * maps them to magnitudes / luptitudes.  Here the variates are Philox4x32-10: one call gives two standard normals by Box-Muller
