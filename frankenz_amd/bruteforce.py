@@ -24,6 +24,7 @@ import numpy as np
 
 from . import pdf as _pdf
 from .engine import HostObjects, get_engine, kde_opts, like_opts, merge_kde_args, pinned_empty
+from .rows import RowConsumers
 
 __all__ = ["BruteForce"]
 
@@ -200,7 +201,7 @@ class _Prepared(object):
         return pdfs, lmap, levid
 
 
-class BruteForce():
+class BruteForce(RowConsumers):
     """Fits data and generates predictions using a brute-force search over all
     models (bruteforce.py:30-34)."""
 
@@ -472,92 +473,27 @@ class BruteForce():
             sys.stderr.flush()
         return (idx, (lmap, levid)) if return_gof else idx
 
-    def sample(self, Nsamples, logwt=None, rstate=None, draws='device', return_gof=False):
-        """Extension, the analogue of ``predict``: ``Nsamples`` draws per object from stored fits (``fit_lnprob``) or the given
-        ``(Ndata, Nmodel)`` rows of ln-weights (NumPy or a device array).  ``fit()`` followed by ``sample()`` gives what
-        ``fit_sample`` gives."""
-        S = _check_nsamples(Nsamples)
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        lw = logwt if hasattr(logwt, "data_ptr") else np.ascontiguousarray(logwt, dtype=np.float64)
-        if len(lw.shape) != 2 or (hasattr(lw, "data_ptr") and not (_is_kind(lw, 'float64') and lw.is_contiguous())):
-            raise ValueError("`logwt` must be a C-contiguous float64 (Ndata, Nmodel) array; got shape %s" % (tuple(lw.shape),))
-        Ndata = int(lw.shape[0])
-        u, key = _draw_uniforms(rstate, draws, Ndata, S)
-        self.philox_key = key
-        eng = get_engine(self._device)
-        idx, lmap, levid = _draw_outputs(eng, None, Ndata, S, like=lw)
-        if Ndata:
-            eng.draw_logwt(lw, S, idx, u=u, key=key, lmap=lmap, levid=levid, n=Ndata, W=int(lw.shape[1]))
-        return (idx, (lmap, levid)) if return_gof else idx
-
     # ------------------------------------------------------------------
-    def weight_sampler(self):
-        """Extension: a ``samplers.model_weight_sampler`` over the stored dense ``fit_lnlike`` rows, for hierarchical re-weighting of
-        the training set (docs/model_weights.md).  Dense rows are for model sets that fit as ``(Ndata, Nmodel)``."""
-        from .samplers import model_weight_sampler
-        if self.fit_lnlike is None:
-            raise ValueError("Fits have not been computed.")
-        return model_weight_sampler(self.fit_lnlike, device=self._device)
-
-    def weight_em(self):
-        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
-        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
-        from .samplers import model_weight_em
-        if self.fit_lnlike is None:
-            raise ValueError("Fits have not been computed.")
-        return model_weight_em(self.fit_lnlike, device=self._device)
-
-    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
-        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
-        posterior mean redshift without a grid -- under the stored dense ``fit_lnprob`` rows or the given ``(Ndata, Nmodel)`` rows
-        (``pdf.posterior_moments``).  ``use_scale`` multiplies each model's values by its fitted ``fit_scale``."""
-        from .pdf import posterior_moments
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_phot: rows.RowConsumers, over the stored dense
+    # (Ndata, Nmodel) rows or given ones
+    def _row_source(self, logwt, shaped=False, use_scale=False):
         if logwt is None:
             logwt = self.fit_lnprob
         if logwt is None:
             raise ValueError("Fits have not been computed and weights have not been provided.")
         if use_scale and self.fit_scale is None:
             raise ValueError("Fits have not been computed: no scales to use.")
-        return posterior_moments(logwt, values, value_errs, value_mask, scale=self.fit_scale if use_scale else None, device=self._device)
+        if shaped:
+            lw = logwt if hasattr(logwt, "data_ptr") else np.ascontiguousarray(logwt, dtype=np.float64)
+            if len(lw.shape) != 2 or (hasattr(lw, "data_ptr") and not (_is_kind(lw, 'float64') and lw.is_contiguous())):
+                raise ValueError("`logwt` must be a C-contiguous float64 (Ndata, Nmodel) array; got shape %s" % (tuple(lw.shape),))
+            logwt = lw
+        return logwt, None, None
 
-    def predict_bins(self, model_labels, model_label_errs, label_bins, logwt=None, wt_thresh=1e-3, normalize=True, return_outside=False,
-                     out=None):
-        """Extension (docs/bins.md): probability per bin of ``label_bins`` (the edges) under the stored dense ``fit_lnprob`` rows or
-        the given ``(Ndata, Nmodel)`` rows, each model a Gaussian ``N(model_labels, model_label_errs)`` integrated exactly between
-        the edges (``pdf.posterior_bins``): the ``(Ndata, Nbins)`` stack ``samplers.population_sampler`` and
-        ``hierarchical_sampler`` take, without a grid."""
-        from .pdf import posterior_bins
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_bins(logwt, model_labels, model_label_errs, label_bins, wt_thresh=wt_thresh, normalize=normalize,
-                              return_outside=return_outside, out=out, device=self._device)
-
-    def predict_cdf(self, model_labels, model_label_errs, points, logwt=None, wt_thresh=1e-3):
-        """Extension (docs/bins.md): the mixture CDF of the same kernel at ``points`` (``pdf.posterior_cdf``); one point per object,
-        ``(Ndata,)``, is the PIT of a validation sample."""
-        from .pdf import posterior_cdf
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_cdf(logwt, model_labels, model_label_errs, points, wt_thresh=wt_thresh, device=self._device)
-
-    def predict_phot(self, logwt=None):
-        """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
-        mean and variance of ``scale * model flux`` per band under the stored fits, the model errors added as the law of total
-        variance, masked model bands left out per band (``share``: the weight that was not)."""
-        from .pdf import posterior_moments
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_moments(logwt, self.models, self.models_err, self.models_mask, scale=self.fit_scale, return_share=True,
-                                 device=self._device)
+    def _lnlike_rows(self):
+        if self.fit_lnlike is None:
+            raise ValueError("Fits have not been computed.")
+        return self.fit_lnlike, None, None, None
 
     def fit_sparse(self, data, data_err, data_mask, Nkeep=256, wt_thresh=1e-3, lprob_func=None, lprob_args=None, lprob_kwargs=None,
                    track_scale=False, resident=False, verbose=True):

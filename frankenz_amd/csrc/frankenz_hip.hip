@@ -1263,6 +1263,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_nzmc_host.inc"
 #include "fz_diag_host.inc"
 #include "fz_synphot_host.inc"
+#include "fz_rows_host.inc"
 #include "fz_draw_host.inc"
 #include "fz_sparse_host.inc"
 #include "fz_mw_host.inc"

@@ -5,10 +5,10 @@
 //                           q = +inf, which the row kernel reads as "step function".  A label that is not finite, or an error that is
 //                           negative or nan, leaves the smallest such model in *badmodel (atomicMin on integers).
 //   k_bins_check_points     a device array of CDF points: any that is not finite sets FZ_BINS_ERR_POINT
-//   k_row_bins<WPO, CDF>   one object per group of WPO waves -- k_row_moments' geometry, a function of the row length alone.  Thread q
+//   k_row_bins<WPO, CDF>   one object per group of WPO waves -- the row consumers' geometry (RowGeom, fz_rows.h).  Thread q
 //                           of the object's 64 WPO owns the entries q, q + 64 WPO, ... and keeps the sums of up to FZ_BINS_BB bins (CDF:
 //                           points) in registers; more bins take ceil(NB / FZ_BINS_BB) passes over the row, each with the weights recomputed
-//                           (the same bits) and the records gathered again from cache.  Walk 0 is k_row_moments': the max, a nan, and
+//                           (the same bits) and the records gathered again from cache.  Walk 0 is row_walk0 (fz_rows.h): the max, a nan, and
 //                           EVERY counted index against [0, M) -- nothing is gathered for a row that fails.  An excluded entry leaves the
 //                           loop before any erfc.  Within a pass the kernel CDF is carried from one edge to the next: one erfc per edge.
 //
@@ -63,46 +63,20 @@ static __global__ __launch_bounds__(256) void k_row_bins(const double* __restric
     constexpr int BB = FZ_BINS_BB;
     __shared__ double shw[4][BB + 3];                                // the wave sums of a pass (WPO == 4), then Z, below, above
     __shared__ double shp[4 / WPO][FZ_BINS_MAX];                     // the object's sums, bin by bin
-    constexpr int OPB = 4 / WPO, NT = 64 * WPO;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int obj = wave / WPO, sub = wave % WPO;
-    const int64_t i = (int64_t)blockIdx.x * OPB + obj;
-    const bool live = i < N;
+    RowGeom<WPO> g(N);
+    constexpr int NT = RowGeom<WPO>::NT;
+    const int lane = g.lane, wave = g.wave, obj = g.obj, sub = g.sub;
+    const int64_t i = g.i, t0 = g.t0();
+    const bool live = g.live;
     const int NB = CDF ? P : P - 1;
-    int64_t n = 0;
-    bool badn = false;
-    if (live) {
-        n = nnb ? nnb[i] : W;
-        if (n < 0 || n > W) { n = 0; badn = true; if (lane == 0 && sub == 0) atomicOr(errflag, FZ_MW_ERR_NNB); }
-    }
-    const double* r = rows + (live ? i : 0) * W;
-    const int64_t* nb = nbr ? nbr + (live ? i : 0) * W : nullptr;
-    const double* xp = x + (live ? i : 0) * xstride;
-    const int64_t t0 = sub * 64 + lane;
+    const int64_t n = g.counted(nnb, W, errflag, FZ_MW_ERR_NNB);
+    const double* r = g.row(rows, W);
+    const int64_t* nb = g.opt(nbr, W);
+    const double* xp = g.row(x, xstride);
 
     // ---- walk 0: the max, a nan, and every counted index (before anything is gathered) ----
-    double m = -INFINITY;
-    bool isnan = false, bad = false;
-    for (int64_t t = t0; t < n; t += NT) {
-        const double v = r[t];
-        isnan |= v != v;
-        m = fmax(m, v);
-        if (nb) { const int64_t j = nb[t]; bad |= j < 0 || j >= M; }
-    }
-    m = wave_max(m);
-    const bool wbad = __any(bad);
-    bool unfit = __any(isnan) || wbad;
-    if (wbad && lane == 0) atomicOr(errflag, FZ_MW_ERR_NBR);
-    if constexpr (WPO > 1) {
-        if (lane == 0) { shw[wave][0] = m; shw[wave][1] = unfit ? 1.0 : 0.0; }
-        __syncthreads();
-        m = -INFINITY; unfit = false;
-#pragma unroll
-        for (int w = 0; w < WPO; ++w) { m = fmax(m, shw[obj * WPO + w][0]); unfit |= shw[obj * WPO + w][1] != 0.0; }
-        __syncthreads();
-    }
-    const bool ok = live && !badn && !unfit && (m - m == 0.0);
+    double m;
+    const bool ok = row_walk0<WPO>(g, r, nb, n, M, shw, errflag, m);
     const int64_t ne = ok ? n : 0;                                   // a row without a posterior walks nothing below
 
     // ---- the passes: BB bins (points) each ----

@@ -1,21 +1,18 @@
 // Host side of the posterior bin masses and mixture CDFs (fz_bins.h; docs/bins.md): fz_row_bins, fz_row_cdf.
-// Included by frankenz_hip.hip after fz_moments_host.inc (mw_limits and the error flags of d_mw[0] come from fz_mw_host.inc).
+// Included by frankenz_hip.hip after fz_rows_host.inc (geometry, entry checks, the error flags of d_mw[0], the chunk loop).
 // Scratch: d_bins[0..2] a host caller's staged rows, neighbours and counts; d_bins[3] its per-object points; d_bins[4..6] the masses
 // (CDF values), below and above going back; d_bins[7] the model records.  The label tables as given, the edges or shared points and
 // nskip go through d_net.
 
 namespace {
-// n device rows, enqueued: the geometry is k_draw's, a function of W alone (FZ_DRAW_WPO = 1 / 4 forces one: tests)
+// n device rows, enqueued: row_geometry's geometry
 template <bool CDF>
 void bins_launch(fz_ctx* c, int64_t n, int64_t W, const double* rows, const int64_t* nbr, const int64_t* nnb, int64_t M, const double2* rec,
                  const double* x, int64_t xstride, int P, double lncut, bool normalize, double* out, double* below, double* above,
                  unsigned long long* nskip, int* d_flags) {
-    int wpo = W <= FZ_DRAW_WAVE_LMAX ? 1 : 4;
-    const long long forced = fz_dbg_int("FZ_DRAW_WPO", 0);
-    if (forced == 1 || forced == 4) wpo = (int)forced;
-    const int opb = 4 / wpo;
-    const dim3 grid((unsigned)((n + opb - 1) / opb)), blk(256);
-    if (wpo == 1) hipLaunchKernelGGL((fz::k_row_bins<1, CDF>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, M, rec, x, xstride, P, lncut, normalize, out, below, above, nskip, d_flags);
+    const RowGeometry geo = row_geometry(W);
+    const dim3 grid = geo.grid(n), blk(256);
+    if (geo.wpo == 1) hipLaunchKernelGGL((fz::k_row_bins<1, CDF>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, M, rec, x, xstride, P, lncut, normalize, out, below, above, nskip, d_flags);
     else hipLaunchKernelGGL((fz::k_row_bins<4, CDF>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, M, rec, x, xstride, P, lncut, normalize, out, below, above, nskip, d_flags);
 }
 
@@ -25,19 +22,17 @@ int bins_run(fz_ctx* c, const char* who, const double* rows, int64_t N, int64_t 
              const double* labels, const double* label_errs, const double* points, int64_t P, bool per_object, double lncut, bool normalize,
              double* out, double* below, double* above, int64_t* nskip) {
     if (!c || !rows || !labels || !label_errs || !points || !out || !nskip) return fail(-1, "%s: NULL argument", who);
-    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "%s: neighbors and nnbr come together", who);
+    FZCHK(rows_entry(who, neighbors, nnbr, N, W, M));
     if (CDF ? P < 1 : P < 2) return fail(-4, CDF ? "%s: %lld points" : "%s: %lld bin edges, a bin needs two", who, (long long)P);
     const int64_t NB = CDF ? P : P - 1;
     if (NB > FZ_BINS_MAX) return fail(-5, "%s: %lld %s, the limit is %d (FZ_BINS_MAX)", who, (long long)NB, CDF ? "points" : "bins", FZ_BINS_MAX);
-    FZCHK(mw_limits(who, W, M, neighbors == nullptr));
-    if (N < 0) return fail(-4, "%s: %lld objects", who, (long long)N);
     if (!(lncut < 0.0)) return fail(-4, "%s: the cut ln(wt_thresh) must be negative (-inf: none)", who);
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {rows, neighbors, nnbr, labels, label_errs, points, out, below, above, nskip}));
     const size_t orow = (size_t)NB * 8;
-    const StageRows rv(c, rows, (size_t)W * 8, c->d_bins[0], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_bins[1], STAGE_IN),
-        cv(c, nnbr, 8, c->d_bins[2], STAGE_IN), pv(c, per_object ? points : nullptr, (size_t)P * 8, c->d_bins[3], STAGE_IN),
-        ov(c, out, orow, c->d_bins[4], STAGE_OUT), bv(c, below, 8, c->d_bins[5], STAGE_OUT), av(c, above, 8, c->d_bins[6], STAGE_OUT);
+    RowsIn in(c, rows, neighbors, nnbr, W, c->d_bins[0], c->d_bins[1], c->d_bins[2]);
+    StageRows pv(c, per_object ? points : nullptr, (size_t)P * 8, c->d_bins[3], STAGE_IN), ov(c, out, orow, c->d_bins[4], STAGE_OUT),
+        bv(c, below, 8, c->d_bins[5], STAGE_OUT), av(c, above, 8, c->d_bins[6], STAGE_OUT);
     StageWhole st{c};
     const void *d_y, *d_s, *d_x = nullptr; void* d_ns;
     FZCHK(st.in(labels, (size_t)M * 8, &d_y)); FZCHK(st.in(label_errs, (size_t)M * 8, &d_s)); FZCHK(st.out(nskip, 8, &d_ns));
@@ -80,24 +75,17 @@ int bins_run(fz_ctx* c, const char* who, const double* rows, int64_t N, int64_t 
     }
 
     // ---- the rows, in chunks under the workspace limit ----
-    int64_t per_obj = 0;
-    for (const StageRows* s : {&rv, &nv, &cv, &pv, &ov, &bv, &av}) if (s->staged()) per_obj += (int64_t)s->row;
-    int64_t nc = per_obj ? std::min<int64_t>(std::max<int64_t>(1, c->ws_limit / per_obj), 1 << 18) : N;
-    nc = std::max<int64_t>(1, std::min(nc, N));
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        const double *dr, *dp; const int64_t *dn, *dc; double *dout, *db, *da;
-        FZCHK(rv.at(i0, n, &dr)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc)); FZCHK(pv.at(i0, n, &dp));
-        FZCHK(ov.at(i0, n, &dout)); FZCHK(bv.at(i0, n, &db)); FZCHK(av.at(i0, n, &da));
+    FZCHK(for_row_chunks(c, N, in, {&pv, &ov, &bv, &av}, [&](int64_t, int64_t n) {
         {
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-            bins_launch<CDF>(c, n, W, dr, dn, dc, M, (const double2*)d_rec, per_object ? dp : (const double*)d_x, per_object ? P : 0, (int)P, lncut,
-                             normalize, dout, db, da, (unsigned long long*)d_ns, d_flags);
+            bins_launch<CDF>(c, n, W, in.rows(), in.nbr(), in.nnb(), M, (const double2*)d_rec, per_object ? pv.as<const double>() : (const double*)d_x,
+                             per_object ? P : 0, (int)P, lncut, normalize, ov.as<double>(), bv.as<double>(), av.as<double>(),
+                             (unsigned long long*)d_ns, d_flags);
         }
         HIPCHK(hipGetLastError());
-        FZCHK(ov.back(i0, n)); FZCHK(bv.back(i0, n)); FZCHK(av.back(i0, n));
-    }
-    FZCHK(mom_flags_check(c, who, W, M));
+        return 0;
+    }));
+    FZCHK(row_flags_check(c, who, W, M));
     FZCHK(st.finish());
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;

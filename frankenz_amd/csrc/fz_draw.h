@@ -21,11 +21,11 @@
 #pragma once
 #include "fz_device.h"
 #include "fz_philox.h"
+#include "fz_rows.h"
 
 #define FZ_DRAW_SEG 256                    // entries per segment: 64 lanes x 4
 #define FZ_DRAW_LMAX (1 << 20)             // longest row (4096 segments: 64 KB of LDS)
 #define FZ_DRAW_SMAX (1 << 16)             // most draws per object
-#define FZ_DRAW_WAVE_LMAX 4096             // rows up to here: one wave per object
 #define FZ_DRAW_HDR 8                      // doubles in front of the segment tables: per wave {nan seen}, per object slot {last segment with mass}
 
 namespace fz {
@@ -68,21 +68,15 @@ static __global__ __launch_bounds__(256) void k_draw(const double* __restrict__ 
                                                      int64_t first, int S, int64_t* __restrict__ idx, double* __restrict__ lmap,
                                                      double* __restrict__ levid, int* __restrict__ errflag) {
     extern __shared__ double sm[];
-    constexpr int OPB = 4 / WPO;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int obj = wave / WPO, sub = wave % WPO;
-    const int64_t i = (int64_t)blockIdx.x * OPB + obj;
+    RowGeom<WPO> g(N);
+    const int lane = g.lane, wave = g.wave, obj = g.obj, sub = g.sub;
+    const int64_t i = g.i;
+    const bool live = g.live;
     const int nsegL = (int)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
     double* fk = sm + FZ_DRAW_HDR + (size_t)obj * 2 * nsegL;       // m_k, then f_k
     double* Pk = fk + nsegL;                                        // S_k, then the mass, then P_k
-    const bool live = i < N;
-    int64_t n = 0;
-    if (live) {
-        n = nnb ? nnb[i] : L;
-        if (n < 0 || n > L) { n = 0; if (lane == 0 && sub == 0) atomicExch(errflag, 1); }
-    }
-    const double* in = rows + (live ? i : 0) * L;
+    const int64_t n = g.template counted<true>(nnb, L, errflag, 1);
+    const double* in = g.row(rows, L);
     const int nseg = (int)((n + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
 
     // ---- stage A: the row, once; the next segment's loads are in flight under this one's arithmetic ----

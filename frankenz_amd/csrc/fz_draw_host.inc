@@ -10,7 +10,7 @@ static int draw_limits(const char* who, int64_t L, int64_t S) {
 }
 
 // n rows of L ln-weights in device memory -> idx (n, S), lmap, levid (device; the last two may be nullptr).  u (n, S) on the device, or
-// nullptr: Philox under (k0, k1), object `first` + row.  The geometry is a function of L alone (FZ_DRAW_WPO = 1 / 4 forces one: tests).
+// nullptr: Philox under (k0, k1), object `first` + row.  The geometry is row_geometry's.
 static int run_draw(fz_ctx* c, int64_t n, int64_t L, const double* rows, const int64_t* nbr, const int64_t* nnb, const double* u, uint32_t k0,
                     uint32_t k1, int64_t first, int64_t S, int64_t* idx, double* lmap, double* levid) {
     if (u) {
@@ -22,20 +22,16 @@ static int run_draw(fz_ctx* c, int64_t n, int64_t L, const double* rows, const i
         }));
         if (bad) return fail(-4, "posterior draws: a uniform outside [0, 1]");
     }
-    int wpo = L <= FZ_DRAW_WAVE_LMAX ? 1 : 4;
-    const long long forced = fz_dbg_int("FZ_DRAW_WPO", 0);
-    if (forced == 1 || forced == 4) wpo = (int)forced;
-    const int opb = 4 / wpo;
-    const size_t nsegL = (size_t)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-    const size_t lds = (FZ_DRAW_HDR + (size_t)opb * 2 * nsegL) * 8;
-    if (lds > FZ_LDS_BYTES) return fail(-5, "posterior draws: rows of %lld entries need %zu bytes of LDS at this geometry", (long long)L, lds);
-    const void* kern = wpo == 1 ? (const void*)fz::k_draw<1> : (const void*)fz::k_draw<4>;
+    const RowGeometry geo = row_geometry(L);
+    size_t lds;
+    FZCHK(geo.seg_lds("posterior draws", L, &lds));
+    const void* kern = geo.wpo == 1 ? (const void*)fz::k_draw<1> : (const void*)fz::k_draw<4>;
     HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int ef = 0;
     FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-        const dim3 grid((unsigned)((n + opb - 1) / opb)), blk(256);
-        if (wpo == 1) hipLaunchKernelGGL(fz::k_draw<1>, grid, blk, lds, c->stream, rows, n, L, nbr, nnb, u, k0, k1, first, (int)S, idx, lmap, levid, d_flags);
+        const dim3 grid = geo.grid(n), blk(256);
+        if (geo.wpo == 1) hipLaunchKernelGGL(fz::k_draw<1>, grid, blk, lds, c->stream, rows, n, L, nbr, nnb, u, k0, k1, first, (int)S, idx, lmap, levid, d_flags);
         else hipLaunchKernelGGL(fz::k_draw<4>, grid, blk, lds, c->stream, rows, n, L, nbr, nnb, u, k0, k1, first, (int)S, idx, lmap, levid, d_flags);
         return 0;
     }));
@@ -64,23 +60,17 @@ extern "C" int fz_draw_logwt(fz_ctx* c, const double* logwt, int64_t N, int64_t 
                              const double* u, uint32_t key0, uint32_t key1, int64_t first, int64_t S, int64_t* idx, double* lmap,
                              double* levid) {
     if (!c || !logwt || !idx) return fail(-1, "fz_draw_logwt: NULL argument");
-    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "fz_draw_logwt: neighbors and nnbr come together");
+    FZCHK(rows_together("fz_draw_logwt", neighbors, nnbr));
     FZCHK(draw_limits("fz_draw_logwt", W, S));
     if (N <= 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {logwt, neighbors, nnbr, u, idx, lmap, levid}));
-    const StageRows rv(c, logwt, (size_t)W * 8, c->d_draw[2], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_draw[0], STAGE_IN),
-        cv(c, nnbr, 8, c->d_draw[1], STAGE_IN);
-    const DrawArgs da(c, u, S, idx, lmap, levid);
-    const int64_t per_obj = (rv.staged() ? W * 8 : 0) + (nv.staged() ? W * 8 + 8 : 0) + da.staged_bytes_per_obj();
-    int64_t nc = std::max<int64_t>(1, c->ws_limit / per_obj);
-    nc = std::min<int64_t>(std::min<int64_t>(nc, N), 1 << 18);
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        const double* dr; const int64_t* dn; const int64_t* dc;
-        FZCHK(rv.at(i0, n, &dr)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc));
-        FZCHK(da.run(c, i0, n, W, dr, dn, dc, key0, key1, first, S));
-    }
+    RowsIn in(c, logwt, neighbors, nnbr, W, c->d_draw[2], c->d_draw[0], c->d_draw[1]);
+    DrawArgs da(c, u, S, idx, lmap, levid);
+    FZCHK(for_row_chunks(c, N, in, {&da.uv, &da.iv, &da.lmv, &da.lev}, [&](int64_t i0, int64_t n) {
+        return run_draw(c, n, W, in.rows(), in.nbr(), in.nnb(), da.uv.as<const double>(), key0, key1, first + i0, S, da.iv.as<int64_t>(),
+                        da.lmv.as<double>(), da.lev.as<double>());
+    }));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -1,11 +1,10 @@
 // Posterior moments of per-model values under rows of ln-weights, and the per-band sums of the zero-point fit (docs/predictive.md;
 // extension, no reference counterpart; the law is stated in include/frankenz_hip.h).
 //
-//   k_row_moments<LB, WPO>  one object per group of WPO waves (1: rows of <= FZ_DRAW_WAVE_LMAX entries, four objects per block; 4: a
-//                      block per object -- k_draw's geometry, a function of the row length alone).  Thread q of the object's 64 WPO
-//                      owns the entries q, q + 64 WPO, ... and keeps the sums of up to LB columns in registers.  Three walks over the
-//                      row: (0) max, nan, and EVERY counted index against [0, M) -- nothing is gathered for a row that fails;
-//                      (1) w = exp(r - m), Z, Z_l, sum w c; (2) the central sums sum w (c - mean_l)^2 and sum w (s Ve)^2, with w
+//   k_row_moments<LB, WPO>  one object per group of WPO waves: the row consumers' geometry (RowGeom, fz_rows.h), a function of the row
+//                      length alone.  Thread q of the object's 64 WPO owns the entries q, q + 64 WPO, ... and keeps the sums of up to
+//                      LB columns in registers.  Three walks over the row: (0) row_walk0 (fz_rows.h): max, nan, and EVERY counted
+//                      index against [0, M) -- nothing is gathered for a row that fails; (1) w = exp(r - m), Z, Z_l, sum w c; (2) the central sums sum w (c - mean_l)^2 and sum w (s Ve)^2, with w
 //                      recomputed (the same bits) and the records re-gathered from cache.
 //   k_mom_pack         the value, error and mask tables of a call -> one record per model (below)
 //   k_phot_sums        block (strip, band): the sums A, B, C and the counts n, nclip of one band over a strip of NZ_CHUNK objects
@@ -72,45 +71,19 @@ static __global__ __launch_bounds__(256) void k_row_moments(const double* __rest
                                                             int* __restrict__ errflag) {
     static_assert(LB <= FZ_MOM_LMAX, "column bucket");
     __shared__ double sh[4][2 * FZ_MOM_LMAX + 2];
-    constexpr int OPB = 4 / WPO, NT = 64 * WPO;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int obj = wave / WPO, sub = wave % WPO;
-    const int64_t i = (int64_t)blockIdx.x * OPB + obj;
-    const bool live = i < N;
-    int64_t n = 0;
-    bool badn = false;
-    if (live) {
-        n = nnb ? nnb[i] : W;
-        if (n < 0 || n > W) { n = 0; badn = true; if (lane == 0 && sub == 0) atomicOr(errflag, FZ_MW_ERR_NNB); }
-    }
-    const double* r = rows + (live ? i : 0) * W;
-    const int64_t* nb = nbr ? nbr + (live ? i : 0) * W : nullptr;
-    const double* sc = scale ? scale + (live ? i : 0) * W : nullptr;
-    const int64_t t0 = sub * 64 + lane;
+    RowGeom<WPO> g(N);
+    constexpr int NT = RowGeom<WPO>::NT;
+    const int lane = g.lane, wave = g.wave, obj = g.obj, sub = g.sub;
+    const int64_t i = g.i, t0 = g.t0();
+    const bool live = g.live;
+    const int64_t n = g.counted(nnb, W, errflag, FZ_MW_ERR_NNB);
+    const double* r = g.row(rows, W);
+    const int64_t* nb = g.opt(nbr, W);
+    const double* sc = g.opt(scale, W);
 
     // ---- walk 0: the max, a nan, and every counted index (before anything is gathered) ----
-    double m = -INFINITY;
-    bool isnan = false, bad = false;
-    for (int64_t t = t0; t < n; t += NT) {
-        const double v = r[t];
-        isnan |= v != v;
-        m = fmax(m, v);
-        if (nb) { const int64_t j = nb[t]; bad |= j < 0 || j >= M; }
-    }
-    m = wave_max(m);
-    const bool wbad = __any(bad);
-    bool unfit = __any(isnan) || wbad;
-    if (wbad && lane == 0) atomicOr(errflag, FZ_MW_ERR_NBR);
-    if constexpr (WPO > 1) {
-        if (lane == 0) { sh[wave][0] = m; sh[wave][1] = unfit ? 1.0 : 0.0; }
-        __syncthreads();
-        m = -INFINITY; unfit = false;
-#pragma unroll
-        for (int w = 0; w < WPO; ++w) { m = fmax(m, sh[obj * WPO + w][0]); unfit |= sh[obj * WPO + w][1] != 0.0; }
-        __syncthreads();
-    }
-    const bool ok = live && !badn && !unfit && (m - m == 0.0);
+    double m;
+    const bool ok = row_walk0<WPO>(g, r, nb, n, M, sh, errflag, m);
     const int64_t ne = ok ? n : 0;                                   // a row without a posterior walks nothing below
 
     // ---- walk 1: Z, Z_l, sum w c ----

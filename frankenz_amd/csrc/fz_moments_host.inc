@@ -1,37 +1,25 @@
 // Host side of the posterior moments and the zero-point sums (fz_moments.h; docs/predictive.md): fz_row_moments, fz_phot_sums.
-// Included by frankenz_hip.hip after fz_mw_em_host.inc (mw_limits, the error flags of d_mw[0]).
+// Included by frankenz_hip.hip after fz_rows_host.inc (geometry, entry checks, the error flags of d_mw[0], the chunk loop).
 // Scratch: d_mom[0..6] a host caller's staged rows, neighbours, counts, scales and the mean / var / share rows going back (fz_phot_sums:
 // x, xe, xm, mean, var); d_mom[7] the strip partials of fz_phot_sums; d_mom[8] the model records of fz_row_moments.  The value tables
 // as given and the small results go through d_net.
 
 namespace {
-int mom_flags_check(fz_ctx* c, const char* who, int64_t W, int64_t M) {
-    int ef = 0;
-    HIPCHK(hipGetLastError());
-    FZCHK(copy_out(c, &ef, c->d_mw[0].p, sizeof(int)));
-    if (ef & FZ_MW_ERR_NNB) return fail(-3, "%s: Nneighbors outside [0, %lld]", who, (long long)W);
-    if (ef & FZ_MW_ERR_NBR) return fail(-3, "%s: a neighbour index outside [0, %lld)", who, (long long)M);
-    return 0;
-}
 template <int LB>
-void mom_launch_lb(fz_ctx* c, int wpo, int64_t n, int64_t W, const double* rows, const int64_t* nbr, const int64_t* nnb, const double* scale, int64_t M,
+void mom_launch_lb(fz_ctx* c, int64_t n, int64_t W, const double* rows, const int64_t* nbr, const int64_t* nnb, const double* scale, int64_t M,
                    int L, const double* rec, int RS, bool has_ve, double* mean, double* var, double* share, unsigned long long* nskip, int* d_flags) {
-    const int opb = 4 / wpo;
-    const dim3 grid((unsigned)((n + opb - 1) / opb)), blk(256);
-    if (wpo == 1) hipLaunchKernelGGL((fz::k_row_moments<LB, 1>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
+    const RowGeometry geo = row_geometry(W);
+    const dim3 grid = geo.grid(n), blk(256);
+    if (geo.wpo == 1) hipLaunchKernelGGL((fz::k_row_moments<LB, 1>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
     else hipLaunchKernelGGL((fz::k_row_moments<LB, 4>), grid, blk, 0, c->stream, rows, n, W, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
 }
-// n device rows, enqueued: the geometry is k_draw's, a function of W alone (FZ_DRAW_WPO = 1 / 4 forces one: tests); the column bucket
-// is the smallest of 4, 8, 16, 32 that holds L
+// n device rows, enqueued: row_geometry's geometry; the column bucket is the smallest of 4, 8, 16, 32 that holds L
 void mom_launch(fz_ctx* c, int64_t n, int64_t W, const double* rows, const int64_t* nbr, const int64_t* nnb, const double* scale, int64_t M, int L,
                 const double* rec, int RS, bool has_ve, double* mean, double* var, double* share, unsigned long long* nskip, int* d_flags) {
-    int wpo = W <= FZ_DRAW_WAVE_LMAX ? 1 : 4;
-    const long long forced = fz_dbg_int("FZ_DRAW_WPO", 0);
-    if (forced == 1 || forced == 4) wpo = (int)forced;
-    if (L <= 4) mom_launch_lb<4>(c, wpo, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
-    else if (L <= 8) mom_launch_lb<8>(c, wpo, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
-    else if (L <= 16) mom_launch_lb<16>(c, wpo, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
-    else mom_launch_lb<32>(c, wpo, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
+    if (L <= 4) mom_launch_lb<4>(c, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
+    else if (L <= 8) mom_launch_lb<8>(c, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
+    else if (L <= 16) mom_launch_lb<16>(c, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
+    else mom_launch_lb<32>(c, n, W, rows, nbr, nnb, scale, M, L, rec, RS, has_ve, mean, var, share, nskip, d_flags);
 }
 }  // namespace
 
@@ -39,17 +27,14 @@ extern "C" int fz_row_moments(fz_ctx* c, const double* rows, int64_t N, int64_t 
                               int64_t M, int32_t L, const double* values, const double* value_errs, const double* value_mask, double* mean,
                               double* var, double* share, int64_t* nskip) {
     if (!c || !rows || !values || !mean || !nskip) return fail(-1, "fz_row_moments: NULL argument");
-    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "fz_row_moments: neighbors and nnbr come together");
+    FZCHK(rows_entry("fz_row_moments", neighbors, nnbr, N, W, M));
     if (L < 1) return fail(-4, "fz_row_moments: %d value columns", (int)L);
     if (L > FZ_MOM_LMAX) return fail(-5, "fz_row_moments: %d value columns, the limit is %d (FZ_MOM_LMAX)", (int)L, FZ_MOM_LMAX);
-    FZCHK(mw_limits("fz_row_moments", W, M, neighbors == nullptr));
-    if (N < 0) return fail(-4, "fz_row_moments: %lld objects", (long long)N);
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {rows, neighbors, nnbr, scale, values, value_errs, value_mask, mean, var, share, nskip}));
-    const StageRows rv(c, rows, (size_t)W * 8, c->d_mom[0], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_mom[1], STAGE_IN),
-        cv(c, nnbr, 8, c->d_mom[2], STAGE_IN), sv(c, scale, (size_t)W * 8, c->d_mom[3], STAGE_IN),
-        mv(c, mean, (size_t)L * 8, c->d_mom[4], STAGE_OUT), vv(c, var, (size_t)L * 8, c->d_mom[5], STAGE_OUT),
-        hv(c, share, (size_t)L * 8, c->d_mom[6], STAGE_OUT);
+    RowsIn in(c, rows, neighbors, nnbr, W, c->d_mom[0], c->d_mom[1], c->d_mom[2]);
+    StageRows sv(c, scale, (size_t)W * 8, c->d_mom[3], STAGE_IN), mv(c, mean, (size_t)L * 8, c->d_mom[4], STAGE_OUT),
+        vv(c, var, (size_t)L * 8, c->d_mom[5], STAGE_OUT), hv(c, share, (size_t)L * 8, c->d_mom[6], STAGE_OUT);
     StageWhole st{c};
     const void *d_v, *d_ve, *d_vm; void* d_ns;
     FZCHK(st.in(values, (size_t)M * L * 8, &d_v)); FZCHK(st.in(value_errs, (size_t)M * L * 8, &d_ve));
@@ -66,24 +51,16 @@ extern "C" int fz_row_moments(fz_ctx* c, const double* rows, int64_t N, int64_t 
         hipLaunchKernelGGL(fz::k_mom_pack, dim3((unsigned)((M * RS + 255) / 256)), dim3(256), 0, c->stream, (const double*)d_v, (const double*)d_ve,
                            (const double*)d_vm, M, (int)L, RS, d_rec);
     }
-    int64_t per_obj = 0;
-    for (const StageRows* s : {&rv, &nv, &cv, &sv, &mv, &vv, &hv}) if (s->staged()) per_obj += (int64_t)s->row;
-    int64_t nc = per_obj ? std::min<int64_t>(std::max<int64_t>(1, c->ws_limit / per_obj), 1 << 18) : N;
-    nc = std::max<int64_t>(1, std::min(nc, N));
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        const double *dr, *ds; const int64_t *dn, *dc; double *dm, *dv, *dh;
-        FZCHK(rv.at(i0, n, &dr)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc)); FZCHK(sv.at(i0, n, &ds));
-        FZCHK(mv.at(i0, n, &dm)); FZCHK(vv.at(i0, n, &dv)); FZCHK(hv.at(i0, n, &dh));
+    FZCHK(for_row_chunks(c, N, in, {&sv, &mv, &vv, &hv}, [&](int64_t, int64_t n) {
         {
             Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-            mom_launch(c, n, W, dr, dn, dc, ds, M, (int)L, (const double*)d_rec, RS, value_errs != nullptr, dm, dv, dh,
-                       (unsigned long long*)d_ns, d_flags);
+            mom_launch(c, n, W, in.rows(), in.nbr(), in.nnb(), sv.as<const double>(), M, (int)L, (const double*)d_rec, RS, value_errs != nullptr,
+                       mv.as<double>(), vv.as<double>(), hv.as<double>(), (unsigned long long*)d_ns, d_flags);
         }
         HIPCHK(hipGetLastError());
-        FZCHK(mv.back(i0, n)); FZCHK(vv.back(i0, n)); FZCHK(hv.back(i0, n));
-    }
-    FZCHK(mom_flags_check(c, "fz_row_moments", W, M));
+        return 0;
+    }));
+    FZCHK(row_flags_check(c, "fz_row_moments", W, M));
     FZCHK(st.finish());
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;

@@ -27,9 +27,8 @@
 #define FZ_MW_TRIES 64                     // attempts of the gamma rejection loop before the call fails
 #define FZ_MW_KEY_XOR 0x6D775F67u          // second key word of the gamma draws: k1 ^ this ("mw_g")
 #define FZ_MW_BOOST_SLOT 128u
-#define FZ_MW_ERR_NNB 1                    // Nneighbors outside [0, W]
-#define FZ_MW_ERR_NBR 2                    // a neighbour index outside [0, M)
-#define FZ_MW_ERR_TRIES 4                  // the rejection loop ran out
+                                           // error bits 1 and 2: FZ_MW_ERR_NNB, FZ_MW_ERR_NBR of every row kernel (fz_rows.h)
+#define FZ_MW_ERR_TRIES 4                 // the rejection loop ran out
 #define FZ_MW_ERR_ALPHA 8                  // alpha_j <= 0 or not finite
 #define FZ_MW_ERR_ZERO 16                  // every gamma draw underflowed: sum(g) == 0, no weights to normalise
 
@@ -57,41 +56,18 @@ __device__ __forceinline__ void mw_load(const double* __restrict__ in, const int
     }
 }
 
-// rows (N, L); nbr (N, L) / nnb (N) or both nullptr (dense rows: L == M, checked by the host); lnw (M); u (N) or nullptr: Philox under
-// (k0, k1) at the counter (first + i, sweep); counts (M), zeroed by the caller; assign (N) or nullptr.
-// Dynamic LDS as k_draw: FZ_DRAW_HDR + (4 / WPO) * 2 * nsegL doubles.
+// Stage A of k_mw_sweep and k_mw_em_rows: k_draw's, on the gathered row in / nb of n counted entries (nseg segments), from the loads
+// to the f_k scaling and its barrier.  On return fk[k] = f_k and Pk[k] = S_k f_k for the object's segments; m: the row's max; R: the
+// register form's copy of the gathered row (REG), which the sweep's stage B draws from.  sm: the block's dynamic LDS (its header takes
+// the waves' flags).  Returns ok: the object is live, no nan, no index that was refused, and the max is finite.
 // REG (WPO == 1, L <= FZ_MW_REG_LMAX: every default k-NN row): the wave keeps the whole gathered row, at most four segments, in
-// registers.  All of its loads are issued at once -- the indices, then the gathers -- instead of segment by segment, and stage B
-// re-reads nothing: it calls draw_segment on the register copy of the hit segment, the values stage A saw, so the draw is the same
-// function of (row, u) as without REG (FZ_MW_REG=0 forces that form: the tests compare them).
+// registers.  All of its loads are issued at once -- the indices, then the gathers -- instead of segment by segment.
 template <int WPO, bool REG>
-static __global__ __launch_bounds__(256) void k_mw_sweep(const double* __restrict__ rows, int64_t N, int64_t L, const int64_t* __restrict__ nbr,
-                                                         const int64_t* __restrict__ nnb, int64_t M, const double* __restrict__ lnw,
-                                                         const double* __restrict__ u, uint32_t k0, uint32_t k1, int64_t first, uint64_t sweep,
-                                                         unsigned long long* __restrict__ counts, int64_t* __restrict__ assign,
-                                                         int* __restrict__ errflag) {
-    extern __shared__ double sm[];
-    constexpr int OPB = 4 / WPO;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int obj = wave / WPO, sub = wave % WPO;
-    const int64_t i = (int64_t)blockIdx.x * OPB + obj;
-    const int nsegL = (int)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-    double* fk = sm + FZ_DRAW_HDR + (size_t)obj * 2 * nsegL;       // m_k, then f_k
-    double* Pk = fk + nsegL;                                        // S_k, then the mass, then P_k
-    const bool live = i < N;
-    int64_t n = 0;
-    if (live) {
-        n = nnb ? nnb[i] : L;
-        if (n < 0 || n > L) { n = 0; if (lane == 0 && sub == 0) atomicOr(errflag, FZ_MW_ERR_NNB); }
-    }
-    const double* in = rows + (live ? i : 0) * L;
-    const int64_t* nb = nbr ? nbr + (live ? i : 0) * L : nullptr;
-    const int nseg = (int)((n + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-
-    // ---- stage A: k_draw's, on the gathered row ----
+__device__ __forceinline__ bool mw_stage_a(const RowGeom<WPO>& g, const double* __restrict__ in, const int64_t* __restrict__ nb,
+                                           const double* __restrict__ lnw, int64_t M, int64_t n, int nseg, double* sm, double* fk, double* Pk,
+                                           int* __restrict__ errflag, double (&R)[REG ? FZ_MW_REG_SEGS : 1][4], double& m) {
+    const int lane = g.lane, wave = g.wave, obj = g.obj, sub = g.sub;
     bool isnan = false, bad = false;
-    double R[REG ? FZ_MW_REG_SEGS : 1][4];
     if constexpr (REG) {
         static_assert(!REG || WPO == 1, "the register form is one wave per object");
         int64_t mm[FZ_MW_REG_SEGS][4];
@@ -144,19 +120,48 @@ static __global__ __launch_bounds__(256) void k_mw_sweep(const double* __restric
         if (wbad) atomicOr(errflag, FZ_MW_ERR_NBR);
     }
     __syncthreads();
-    double m = -INFINITY;
+    m = -INFINITY;
     for (int k = lane; k < nseg; k += 64) m = fmax(m, fk[k]);
     m = wave_max(m);
     bool unfit = false;                                              // a nan, or an index that was refused
 #pragma unroll
     for (int w = 0; w < WPO; ++w) unfit |= sm[obj * WPO + w] != 0.0;
-    const bool ok = live && !unfit && (m - m == 0.0);
     __syncthreads();
     for (int k = sub * 64 + lane; k < nseg; k += WPO * 64) {
         const double f = exp(fk[k] - m);
         fk[k] = f; Pk[k] = Pk[k] * f;
     }
     __syncthreads();
+    return g.live && !unfit && (m - m == 0.0);
+}
+
+// rows (N, L); nbr (N, L) / nnb (N) or both nullptr (dense rows: L == M, checked by the host); lnw (M); u (N) or nullptr: Philox under
+// (k0, k1) at the counter (first + i, sweep); counts (M), zeroed by the caller; assign (N) or nullptr.
+// Dynamic LDS as k_draw: FZ_DRAW_HDR + (4 / WPO) * 2 * nsegL doubles.
+// REG: stage B re-reads nothing: it calls draw_segment on the register copy of the hit segment, the values stage A saw, so the draw is
+// the same function of (row, u) as without REG (FZ_MW_REG=0 forces that form: the tests compare them).
+template <int WPO, bool REG>
+static __global__ __launch_bounds__(256) void k_mw_sweep(const double* __restrict__ rows, int64_t N, int64_t L, const int64_t* __restrict__ nbr,
+                                                         const int64_t* __restrict__ nnb, int64_t M, const double* __restrict__ lnw,
+                                                         const double* __restrict__ u, uint32_t k0, uint32_t k1, int64_t first, uint64_t sweep,
+                                                         unsigned long long* __restrict__ counts, int64_t* __restrict__ assign,
+                                                         int* __restrict__ errflag) {
+    extern __shared__ double sm[];
+    RowGeom<WPO> g(N);
+    const int lane = g.lane, obj = g.obj, sub = g.sub;
+    const int64_t i = g.i;
+    const bool live = g.live;
+    const int nsegL = (int)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
+    double* fk = sm + FZ_DRAW_HDR + (size_t)obj * 2 * nsegL;       // m_k, then f_k
+    double* Pk = fk + nsegL;                                        // S_k, then the mass, then P_k
+    const int64_t n = g.counted(nnb, L, errflag, FZ_MW_ERR_NNB);
+    const double* in = g.row(rows, L);
+    const int64_t* nb = g.opt(nbr, L);
+    const int nseg = (int)((n + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
+
+    // ---- stage A: k_draw's, on the gathered row ----
+    double R[REG ? FZ_MW_REG_SEGS : 1][4], m;
+    const bool ok = mw_stage_a<WPO, REG>(g, in, nb, lnw, M, n, nseg, sm, fk, Pk, errflag, R, m);
     if (sub == 0 && lane == 0) {
         double P = 0.0; int klast = 0;
         for (int k = 0; k < nseg; ++k) { P += Pk[k]; Pk[k] = P; if (fk[k] > 0.0) klast = k; }

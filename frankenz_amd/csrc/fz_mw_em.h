@@ -2,10 +2,14 @@
 // hierarchical_sampler, samplers.py:311-535, with every entry's responsibility added where the sweep draws one and counts).  One
 // iteration from weights w:
 //
-//   k_mw_em_rows<WPO, REG>  per object ell_i = logsumexp_k (r_ik + lnw[nbr_ik]): k_mw_sweep's stage A (the same mw_load, the same index
-//                      check before the gather, the same register form and geometry) without stage B and without the uniform; nan marks
-//                      a row without a posterior.  The stage is COPIED from k_mw_sweep, not shared: sharing it would mean cutting that
-//                      kernel in two around its LDS tables, which changes its instruction stream.
+//   k_mw_em_rows<WPO, REG>  per object ell_i = logsumexp_k (r_ik + lnw[nbr_ik]): k_mw_sweep's stage A (mw_stage_a, fz_mw.h: the same
+//                      mw_load, the same index check before the gather, the same register form and geometry) without stage B and
+//                      without the uniform; nan marks a row without a posterior.  The stage is SHARED with k_mw_sweep, as one
+//                      __forceinline__ function.  Against the copy it replaced, the six instantiations keep their registers (78 / 72 /
+//                      74 VGPRs, no scratch, the same occupancy), their instruction counts move by -12 to +2 of 1 271 to 3 296, and
+//                      their times on 1e6 rows of 500 entries stay within the copy's own spread: sweeps of k_mw_sweep<1, REG> / <1> /
+//                      <4> 11.61 -> 11.63 / 15.40 -> 15.38 / 6.38 -> 6.36 ms per four, k_mw_em_rows 2.860 -> 2.857 / 3.056 -> 3.055 /
+//                      1.550 -> 1.553 ms (docs/model_weights.md); the results are the same bits.
 //   k_mw_em_lsum       block partials of sum(ell) over NZ_CHUNK objects each, in index order, and the count of the skipped rows.  It is
 //                      a pass of its own over ell (N) so that the sum does not depend on the row pass's geometry or on the chunks a
 //                      host caller's rows arrive in.
@@ -42,95 +46,18 @@ static __global__ __launch_bounds__(256) void k_mw_em_rows(const double* __restr
                                                            const int64_t* __restrict__ nnb, int64_t M, const double* __restrict__ lnw,
                                                            double* __restrict__ ell, int* __restrict__ errflag) {
     extern __shared__ double sm[];
-    constexpr int OPB = 4 / WPO;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int obj = wave / WPO, sub = wave % WPO;
-    const int64_t i = (int64_t)blockIdx.x * OPB + obj;
+    RowGeom<WPO> g(N);
     const int nsegL = (int)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-    double* fk = sm + FZ_DRAW_HDR + (size_t)obj * 2 * nsegL;
+    double* fk = sm + FZ_DRAW_HDR + (size_t)g.obj * 2 * nsegL;
     double* Pk = fk + nsegL;
-    const bool live = i < N;
-    int64_t n = 0;
-    if (live) {
-        n = nnb ? nnb[i] : L;
-        if (n < 0 || n > L) { n = 0; if (lane == 0 && sub == 0) atomicOr(errflag, FZ_MW_ERR_NNB); }
-    }
-    const double* in = rows + (live ? i : 0) * L;
-    const int64_t* nb = nbr ? nbr + (live ? i : 0) * L : nullptr;
+    const int64_t n = g.counted(nnb, L, errflag, FZ_MW_ERR_NNB);
     const int nseg = (int)((n + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-
-    bool isnan = false, bad = false;
-    if constexpr (REG) {
-        static_assert(!REG || WPO == 1, "the register form is one wave per object");
-        double R[FZ_MW_REG_SEGS][4];
-        int64_t mm[FZ_MW_REG_SEGS][4];
-#pragma unroll
-        for (int s = 0; s < FZ_MW_REG_SEGS; ++s) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int64_t j = (int64_t)s * FZ_DRAW_SEG + 4 * lane + t;
-                const bool on = j < n;
-                mm[s][t] = on ? (nb ? nb[j] : j) : 0;
-                R[s][t] = on ? in[j] : -INFINITY;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < FZ_MW_REG_SEGS; ++s) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const bool on = (int64_t)s * FZ_DRAW_SEG + 4 * lane + t < n, in_set = mm[s][t] >= 0 && mm[s][t] < M;
-                bad |= on && !in_set;
-                R[s][t] = (on && in_set) ? R[s][t] + lnw[mm[s][t]] : -INFINITY;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < FZ_MW_REG_SEGS; ++s) {
-            if (s < nseg) {
-                double e[4], p[4], x, mk;
-                isnan |= (R[s][0] != R[s][0]) | (R[s][1] != R[s][1]) | (R[s][2] != R[s][2]) | (R[s][3] != R[s][3]);
-                draw_segment(R[s], lane, e, p, x, mk);
-                if (lane == 63) { fk[s] = mk; Pk[s] = x + p[3]; }
-            }
-        }
-    } else {
-        double r[4], rn[4], e[4], p[4], x, mk;
-        if (sub < nseg) mw_load(in, nb, lnw, M, n, sub, lane, r, bad);
-        for (int k = sub; k < nseg; k += WPO) {
-            const bool more = k + WPO < nseg;
-            if (more) mw_load(in, nb, lnw, M, n, k + WPO, lane, rn, bad);
-            isnan |= (r[0] != r[0]) | (r[1] != r[1]) | (r[2] != r[2]) | (r[3] != r[3]);
-            draw_segment(r, lane, e, p, x, mk);
-            if (lane == 63) { fk[k] = mk; Pk[k] = x + p[3]; }
-            if (more) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) r[t] = rn[t];
-            }
-        }
-    }
-    const bool wnan = __any(isnan), wbad = __any(bad);
-    if (lane == 0) {
-        sm[wave] = (wnan ? 1.0 : 0.0) + (wbad ? 2.0 : 0.0);
-        if (wbad) atomicOr(errflag, FZ_MW_ERR_NBR);
-    }
-    __syncthreads();
-    double m = -INFINITY;
-    for (int k = lane; k < nseg; k += 64) m = fmax(m, fk[k]);
-    m = wave_max(m);
-    bool unfit = false;
-#pragma unroll
-    for (int w = 0; w < WPO; ++w) unfit |= sm[obj * WPO + w] != 0.0;
-    const bool ok = live && !unfit && (m - m == 0.0);
-    __syncthreads();
-    for (int k = sub * 64 + lane; k < nseg; k += WPO * 64) {
-        const double f = exp(fk[k] - m);
-        fk[k] = f; Pk[k] = Pk[k] * f;
-    }
-    __syncthreads();
-    if (live && sub == 0 && lane == 0) {
+    double R[REG ? FZ_MW_REG_SEGS : 1][4], m;
+    const bool ok = mw_stage_a<WPO, REG>(g, g.row(rows, L), g.opt(nbr, L), lnw, M, n, nseg, sm, fk, Pk, errflag, R, m);
+    if (g.live && g.sub == 0 && g.lane == 0) {
         double P = 0.0;
         for (int k = 0; k < nseg; ++k) P += Pk[k];
-        ell[i] = ok ? m + log(P) : (double)NAN;
+        ell[g.i] = ok ? m + log(P) : (double)NAN;
     }
 }
 

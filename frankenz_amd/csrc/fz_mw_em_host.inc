@@ -1,5 +1,5 @@
 // Host side of EM over the model weights (fz_mw_em.h; docs/model_weights.md): fz_mw_em_index_bytes, fz_mw_em_index, fz_mw_loglike,
-// fz_mw_em.  Included by frankenz_hip.hip after fz_mw_host.inc (mw_limits, the error flags).
+// fz_mw_em.  Included by frankenz_hip.hip after fz_rows_host.inc and fz_mw_host.inc (mw_limits, the error flags, mw_launch_rows).
 // Scratch: d_mwem[0] ell, [1] partials of sum(ell), [2] segment sums, [3] partials of sum(a) and of the prior term + sum(a),
 // [4] seg_off, [5] scan partials; the index build alone: [6] row starts, [7] [8] keys, [9] [10] objects / values in flight, [11] digit
 // histograms -- released when the build returns.
@@ -8,12 +8,10 @@
 
 namespace {
 int em_flags_check(fz_ctx* c, const char* who, int64_t W, int64_t M) {
-    int ef = 0;
-    HIPCHK(hipGetLastError());
-    FZCHK(copy_out(c, &ef, c->d_mw[0].p, sizeof(int)));
+    int ef;
+    FZCHK(mw_flags_read(c, &ef));
     if (ef & FZ_MW_ERR_ALPHA1) return fail(-4, "%s: alpha must be finite and >= 1 (below 1 the posterior has no maximum)", who);
-    if (ef & FZ_MW_ERR_NNB) return fail(-3, "%s: Nneighbors outside [0, %lld]", who, (long long)W);
-    if (ef & FZ_MW_ERR_NBR) return fail(-3, "%s: a neighbour index outside [0, %lld)", who, (long long)M);
+    FZCHK(row_flags_check(who, ef, W, M));
     if (ef & FZ_MW_ERR_ZERO) return fail(-7, "%s: no object has a posterior under these weights and alpha == 1: no weights to normalise", who);
     return 0;
 }
@@ -23,24 +21,11 @@ int em_limits(const char* who, int64_t N, int64_t W, int64_t M, bool dense) {
     if (N >= FZ_MW_EM_NMAX) return fail(-5, "%s: %lld objects, the limit is N < 2^31 (FZ_MW_EM_NMAX)", who, (long long)N);
     return 0;
 }
-// the row pass over n device rows, enqueued: mw_launch_sweep's geometry
+// the row pass over n device rows, enqueued
 int em_launch_rows(fz_ctx* c, int64_t n, int64_t L, const double* rows, const int64_t* nbr, const int64_t* nnb, int64_t M, const double* lnw,
                    double* ell, int* d_flags) {
-    int wpo = L <= FZ_DRAW_WAVE_LMAX ? 1 : 4;
-    const long long forced = fz_dbg_int("FZ_DRAW_WPO", 0);
-    if (forced == 1 || forced == 4) wpo = (int)forced;
-    const int opb = 4 / wpo;
-    const size_t nsegL = (size_t)((L + FZ_DRAW_SEG - 1) / FZ_DRAW_SEG);
-    const size_t lds = (FZ_DRAW_HDR + (size_t)opb * 2 * nsegL) * 8;
-    if (lds > FZ_LDS_BYTES) return fail(-5, "model weights: rows of %lld entries need %zu bytes of LDS at this geometry", (long long)L, lds);
-    const bool reg = wpo == 1 && L <= FZ_MW_REG_LMAX && fz_dbg_int("FZ_MW_REG", 1) != 0;
-    const void* kern = reg ? (const void*)fz::k_mw_em_rows<1, true> : wpo == 1 ? (const void*)fz::k_mw_em_rows<1, false> : (const void*)fz::k_mw_em_rows<4, false>;
-    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 grid((unsigned)((n + opb - 1) / opb)), blk(256);
-    if (reg) hipLaunchKernelGGL((fz::k_mw_em_rows<1, true>), grid, blk, lds, c->stream, rows, n, L, nbr, nnb, M, lnw, ell, d_flags);
-    else if (wpo == 1) hipLaunchKernelGGL((fz::k_mw_em_rows<1, false>), grid, blk, lds, c->stream, rows, n, L, nbr, nnb, M, lnw, ell, d_flags);
-    else hipLaunchKernelGGL((fz::k_mw_em_rows<4, false>), grid, blk, lds, c->stream, rows, n, L, nbr, nnb, M, lnw, ell, d_flags);
-    return 0;
+    decltype(fz::k_mw_em_rows<1, true>)* const kern[3] = {fz::k_mw_em_rows<1, true>, fz::k_mw_em_rows<1, false>, fz::k_mw_em_rows<4, false>};
+    return mw_launch_rows(c, n, L, kern, rows, n, L, nbr, nnb, M, lnw, ell, d_flags);
 }
 // out[0..n] = the exclusive scan of in[0..n) and its total, enqueued (out may be in)
 int em_scan(fz_ctx* c, const int64_t* in, int64_t n, int64_t* out) {
@@ -144,12 +129,11 @@ extern "C" int fz_mw_em_index(fz_ctx* c, const double* rows, int64_t N, int64_t 
 extern "C" int fz_mw_loglike(fz_ctx* c, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
                              const double* lnw, double* ell, double* lnlike, int64_t* nskip) {
     if (!c || !rows || !lnw || !lnlike || !nskip) return fail(-1, "fz_mw_loglike: NULL argument");
-    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "fz_mw_loglike: neighbors and nnbr come together");
+    FZCHK(rows_together("fz_mw_loglike", neighbors, nnbr));
     FZCHK(em_limits("fz_mw_loglike", N, W, M, neighbors == nullptr));
     HIPCHK(hipSetDevice(c->device));
     FZCHK(wait_for_producers(c, {rows, neighbors, nnbr, lnw, ell, lnlike, nskip}));
-    const StageRows rv(c, rows, (size_t)W * 8, c->d_draw[2], STAGE_IN), nv(c, neighbors, (size_t)W * 8, c->d_draw[0], STAGE_IN),
-        cv(c, nnbr, 8, c->d_draw[1], STAGE_IN);
+    RowsIn in(c, rows, neighbors, nnbr, W, c->d_draw[2], c->d_draw[0], c->d_draw[1]);
     StageWhole st{c};
     const void* d_lnw; void *d_ell, *d_ll, *d_ns;
     FZCHK(st.in(lnw, (size_t)M * 8, &d_lnw)); FZCHK(st.out(ell, (size_t)N * 8, &d_ell));
@@ -158,16 +142,10 @@ extern "C" int fz_mw_loglike(fz_ctx* c, const double* rows, int64_t N, int64_t W
     HIPCHK(hipMemsetAsync(d_ns, 0, 8, c->stream));
     int* d_flags;
     FZCHK(mw_flags_begin(c, &d_flags));
-    const int64_t per_obj = (rv.staged() ? W * 8 : 0) + (nv.staged() ? W * 8 + 8 : 0);
-    int64_t nc = per_obj ? std::min<int64_t>(std::max<int64_t>(1, c->ws_limit / per_obj), 1 << 18) : N;
-    nc = std::max<int64_t>(1, std::min(nc, N));
-    for (int64_t i0 = 0; i0 < N; i0 += nc) {
-        const int64_t n = std::min(nc, N - i0);
-        const double* dr; const int64_t* dn; const int64_t* dc;
-        FZCHK(rv.at(i0, n, &dr)); FZCHK(nv.at(i0, n, &dn)); FZCHK(cv.at(i0, n, &dc));
+    FZCHK(for_row_chunks(c, N, in, {}, [&](int64_t i0, int64_t n) {
         Timer t(c, &c->tm.ms_other, &c->tm.n_other);
-        FZCHK(em_launch_rows(c, n, W, dr, dn, dc, M, (const double*)d_lnw, (double*)d_ell + i0, d_flags));
-    }
+        return em_launch_rows(c, n, W, in.rows(), in.nbr(), in.nnb(), M, (const double*)d_lnw, (double*)d_ell + i0, d_flags);
+    }));
     const int64_t nblkL = (N + NZ_CHUNK - 1) / NZ_CHUNK;
     FZCHK(c->d_mwem[1].ensure((size_t)nblkL * 8));
     {
@@ -187,7 +165,7 @@ extern "C" int fz_mw_em(fz_ctx* c, const double* rows, int64_t N, int64_t W, con
                         const int64_t* col_off, const int32_t* col_obj, const double* col_val, int64_t entries, const double* alpha, double* lnw,
                         int32_t niter, double* pos, double* counts, double* trace, int64_t* nskip) {
     if (!c || !rows || !alpha || !lnw || !pos || !counts || !trace || !nskip) return fail(-1, "fz_mw_em: NULL argument");
-    if ((neighbors == nullptr) != (nnbr == nullptr)) return fail(-1, "fz_mw_em: neighbors and nnbr come together");
+    FZCHK(rows_together("fz_mw_em", neighbors, nnbr));
     const bool dense = neighbors == nullptr;
     FZCHK(em_limits("fz_mw_em", N, W, M, dense));
     if (niter < 1) return fail(-4, "fz_mw_em: %d iterations", (int)niter);

@@ -13,6 +13,8 @@ struct StageRows {
     StageRows() = default;
     StageRows(fz_ctx* c_, const void* p, size_t row_bytes, DevBuf& b, int dir_, bool scratch_ = false)
         : c(c_), host((char*)p), row(row_bytes), buf(&b), dir(dir_), dev(is_device_ptr(p)), scratch(scratch_) {}
+    void* cur = nullptr;                                             // the current chunk's view, where a loop keeps it (for_row_chunks)
+    template <class T> T* as() const { return (T*)cur; }
     bool staged() const { return host && !dev; }
     // the device view: the array itself at row i0, or the buffer, grown and (in / inout) filled with the caller's rows
     template <class T> int at(int64_t i0, int64_t n, T** d) const {

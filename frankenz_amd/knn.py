@@ -22,6 +22,7 @@ import numpy as np
 from . import pdf as _pdf
 from .bruteforce import _check_lprob, _check_nsamples, _device_objects, _draw_outputs, _draw_uniforms, _progress
 from .engine import HostObjects, _digest, get_engine, kde_opts, like_opts, merge_kde_args, pinned_empty
+from .rows import RowConsumers
 
 __all__ = ["NearestNeighbors"]
 
@@ -192,7 +193,7 @@ class _PreparedKnn(object):
         return pdfs, lmap, levid
 
 
-class NearestNeighbors():
+class NearestNeighbors(RowConsumers):
     """Fits data and generates predictions using k-nearest neighbours over Monte-Carlo
     realisations of the models (knn.py:33-38)."""
 
@@ -595,92 +596,24 @@ class NearestNeighbors():
         nn = np.ascontiguousarray(self.Nneighbors, dtype=np.int64)
         if lw.shape != (Ndata, W) or nb.shape != (Ndata, W) or nn.shape != (Ndata,):
             raise ValueError("`logwt` has shape %s; expected (Ndata, K*k) = (%d, %d) like `neighbors`" % (lw.shape, Ndata, W))
-        eng = get_engine(self._device)
-        idx, lmap, levid = _draw_outputs(eng, None, Ndata, S)
-        if Ndata:
-            eng.draw_logwt(lw, S, idx, u=u, key=key, neighbors=nb, nnbr=nn, lmap=lmap, levid=levid, n=Ndata, W=W)
-        return idx, lmap, levid
+        return RowConsumers._draw_rows(self, lw, nb, nn, S, u, key)
 
-    def sample(self, Nsamples, logwt=None, rstate=None, draws='device', return_gof=False):
-        """Extension, the analogue of ``predict``: ``Nsamples`` draws (model indices) per object from the stored fits
-        (``fit_lnprob`` beside ``neighbors`` / ``Nneighbors``) or the given padded ``(Ndata, K*k)`` rows."""
-        S = _check_nsamples(Nsamples)
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_phot: rows.RowConsumers, over the stored padded
+    # (Ndata, K*k) rows beside ``neighbors`` / ``Nneighbors``, or given rows of that layout
+    def _draw_rows(self, lw, neighbors, Nneighbors, S, u, key):
+        return self._draw_stored(lw, S, u, key)
+
+    def _row_source(self, logwt, shaped=False, use_scale=False):
         if logwt is None:
             logwt = self.fit_lnprob
         if logwt is None or getattr(self, "neighbors", None) is None:
             raise ValueError("Fits have not been computed and weights have not been provided.")
-        u, key = _draw_uniforms(rstate, draws, self.NDATA, S)
-        self.philox_key = key
-        idx, lmap, levid = self._draw_stored(logwt, S, u, key)
-        return (idx, (lmap, levid)) if return_gof else idx
+        return logwt, self.neighbors, self.Nneighbors
 
-    def weight_sampler(self):
-        """Extension: a ``samplers.model_weight_sampler`` over the stored fits -- the sparse rows ``fit_lnlike`` beside
-        ``neighbors`` / ``Nneighbors`` -- for hierarchical re-weighting of the training set (docs/model_weights.md)."""
-        from .samplers import model_weight_sampler
+    def _lnlike_rows(self):
         if self.fit_lnlike is None or getattr(self, "neighbors", None) is None:
             raise ValueError("Fits have not been computed.")
-        return model_weight_sampler(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
-                                    device=self._device)
-
-    def weight_em(self):
-        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
-        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
-        from .samplers import model_weight_em
-        if self.fit_lnlike is None or getattr(self, "neighbors", None) is None:
-            raise ValueError("Fits have not been computed.")
-        return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
-                               device=self._device)
-
-    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
-        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
-        posterior mean redshift without a grid -- under the stored fits (``fit_lnprob`` beside ``neighbors`` / ``Nneighbors``) or the
-        given padded ``(Ndata, K*k)`` rows (``pdf.posterior_moments``).  ``use_scale`` multiplies each entry's values by its
-        fitted ``fit_scale``."""
-        from .pdf import posterior_moments
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None or getattr(self, "neighbors", None) is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_moments(logwt, values, value_errs, value_mask, scale=self.fit_scale if use_scale else None,
-                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, device=self._device)
-
-    def predict_bins(self, model_labels, model_label_errs, label_bins, logwt=None, wt_thresh=1e-3, normalize=True, return_outside=False,
-                     out=None):
-        """Extension (docs/bins.md): probability per bin of ``label_bins`` (the edges) under the stored fits (``fit_lnprob`` beside
-        ``neighbors`` / ``Nneighbors``) or the given padded ``(Ndata, K*k)`` rows, each model a Gaussian
-        ``N(model_labels, model_label_errs)`` integrated exactly between the edges (``pdf.posterior_bins``): the ``(Ndata, Nbins)``
-        stack ``samplers.population_sampler`` and ``hierarchical_sampler`` take, without a grid."""
-        from .pdf import posterior_bins
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None or getattr(self, "neighbors", None) is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_bins(logwt, model_labels, model_label_errs, label_bins, neighbors=self.neighbors, Nneighbors=self.Nneighbors,
-                              wt_thresh=wt_thresh, normalize=normalize, return_outside=return_outside, out=out, device=self._device)
-
-    def predict_cdf(self, model_labels, model_label_errs, points, logwt=None, wt_thresh=1e-3):
-        """Extension (docs/bins.md): the mixture CDF of the same kernel at ``points`` (``pdf.posterior_cdf``); one point per object,
-        ``(Ndata,)``, is the PIT of a validation sample."""
-        from .pdf import posterior_cdf
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None or getattr(self, "neighbors", None) is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_cdf(logwt, model_labels, model_label_errs, points, neighbors=self.neighbors, Nneighbors=self.Nneighbors,
-                             wt_thresh=wt_thresh, device=self._device)
-
-    def predict_phot(self, logwt=None):
-        """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
-        mean and variance of ``scale * model flux`` per band under the stored fits, the model errors added as the law of total
-        variance, masked model bands left out per band (``share``: the weight that was not)."""
-        from .pdf import posterior_moments
-        if logwt is None:
-            logwt = self.fit_lnprob
-        if logwt is None or getattr(self, "neighbors", None) is None:
-            raise ValueError("Fits have not been computed and weights have not been provided.")
-        return posterior_moments(logwt, self.models, self.models_err, self.models_mask, scale=self.fit_scale,
-                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, return_share=True, device=self._device)
+        return self.fit_lnlike, self.neighbors, self.Nneighbors, self.NMODEL
 
     # ------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None,

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 
 from .engine import get_engine, kde_opts, merge_kde_args, pinned_empty
+from .rows import RowConsumers
 
 __all__ = ["SparseFits", "WMAX", "LMAX"]
 
@@ -32,7 +33,7 @@ def check_keep(Nkeep, wt_thresh, Nmodel=None):
     return int(Nkeep), (np.log(wt_thresh) if wt_thresh > 0. else -np.inf)
 
 
-class SparseFits(object):
+class SparseFits(RowConsumers):
     """Sparse rows of an exhaustive fit.  ``neighbors`` (Ndata, Nkeep) int64 model indices, best first, padded with -99;
     ``Nneighbors`` (Ndata); the ``fit_*`` arrays (Ndata, Nkeep) padded as ``NearestNeighbors`` pads them (one that was not asked for
     is None); ``lmap`` / ``levid`` of the FULL rows; ``lnkept`` the logsumexp of the kept ln-posteriors; ``NMODEL``."""
@@ -84,75 +85,25 @@ class SparseFits(object):
             sys.stderr.flush()
         return (pdfs, (lmap, levid)) if return_gof else pdfs
 
-    def sample(self, Nsamples, logwt=None, rstate=None, draws='device', return_gof=False):
-        """``Nsamples`` posterior draws (model indices) per object from the sparse rows (``Engine.draw_logwt`` with ``neighbors`` /
-        ``nnbr``); ``draws`` / ``rstate`` as in ``BruteForce.sample``.  ``lmap`` / ``levid`` returned are those of the sparse rows."""
-        from .bruteforce import _check_nsamples, _draw_outputs, _draw_uniforms
-        S = _check_nsamples(Nsamples)
-        lw = self._rows(logwt)
-        u, key = _draw_uniforms(rstate, draws, self.NDATA, S)
-        self.philox_key = key
-        eng = get_engine(self._device)
-        idx, lmap, levid = _draw_outputs(eng, None, self.NDATA, S, like=lw)
-        if self.NDATA:
-            eng.draw_logwt(lw, S, idx, u=u, key=key, neighbors=self.neighbors, nnbr=self.Nneighbors, lmap=lmap, levid=levid, n=self.NDATA,
-                           W=self.NKEEP)
-        return (idx, (lmap, levid)) if return_gof else idx
-
-    def weight_sampler(self):
-        """a ``samplers.model_weight_sampler`` over the sparse ``fit_lnlike`` rows (device-resident arrays are used in place)"""
-        from .samplers import model_weight_sampler
-        if self.fit_lnlike is None:
-            raise ValueError("the ln-likelihood rows were not kept")
-        return model_weight_sampler(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
-                                    device=self._device)
-
-    def weight_em(self):
-        """Extension: a ``samplers.model_weight_em`` over the same rows as ``weight_sampler()``: the maximum-likelihood / MAP weights of
-        the training set and the marginal ln-likelihood of a weight vector (docs/model_weights.md)."""
-        from .samplers import model_weight_em
-        if self.fit_lnlike is None:
-            raise ValueError("the ln-likelihood rows were not kept")
-        return model_weight_em(self.fit_lnlike, neighbors=self.neighbors, Nneighbors=self.Nneighbors, Nmodels=self.NMODEL,
-                               device=self._device)
-
-    def moments(self, values, value_errs=None, value_mask=None, logwt=None, use_scale=False):
-        """Extension (docs/predictive.md): posterior mean and variance of any per-model quantity -- ``moments(z_train, z_err)`` is a
-        posterior mean redshift without a grid -- from the sparse rows (``pdf.posterior_moments``).  ``use_scale`` multiplies each
-        entry's values by its fitted ``fit_scale``."""
-        from .pdf import posterior_moments
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf: rows.RowConsumers, over the sparse rows
+    def _row_source(self, logwt, shaped=False, use_scale=False):
         if use_scale and self.fit_scale is None:
             raise ValueError("the scale rows were not kept (`track_scale=True`)")
-        return posterior_moments(self._rows(logwt), values, value_errs, value_mask, scale=self.fit_scale if use_scale else None,
-                                 neighbors=self.neighbors, Nneighbors=self.Nneighbors, device=self._device)
+        return self._rows(logwt), self.neighbors, self.Nneighbors
 
-    def predict_bins(self, model_labels, model_label_errs, label_bins, logwt=None, wt_thresh=1e-3, normalize=True, return_outside=False,
-                     out=None):
-        """Extension (docs/bins.md): probability per bin of ``label_bins`` (the edges) from the sparse rows, each model a Gaussian
-        ``N(model_labels, model_label_errs)`` integrated exactly between the edges (``pdf.posterior_bins``): the ``(Ndata, Nbins)``
-        stack ``samplers.population_sampler`` and ``hierarchical_sampler`` take, without a grid."""
-        from .pdf import posterior_bins
+    def _lnlike_rows(self):
+        if self.fit_lnlike is None:
+            raise ValueError("the ln-likelihood rows were not kept")
+        return self.fit_lnlike, self.neighbors, self.Nneighbors, self.NMODEL
+
+    def _check_labels(self, model_labels):
         if len(model_labels) != self.NMODEL:
             raise ValueError("%d labels for %d models" % (len(model_labels), self.NMODEL))
-        return posterior_bins(self._rows(logwt), model_labels, model_label_errs, label_bins, neighbors=self.neighbors,
-                              Nneighbors=self.Nneighbors, wt_thresh=wt_thresh, normalize=normalize, return_outside=return_outside, out=out,
-                              device=self._device)
-
-    def predict_cdf(self, model_labels, model_label_errs, points, logwt=None, wt_thresh=1e-3):
-        """Extension (docs/bins.md): the mixture CDF of the same kernel at ``points`` (``pdf.posterior_cdf``); one point per object,
-        ``(Ndata,)``, is the PIT of a validation sample."""
-        from .pdf import posterior_cdf
-        if len(model_labels) != self.NMODEL:
-            raise ValueError("%d labels for %d models" % (len(model_labels), self.NMODEL))
-        return posterior_cdf(self._rows(logwt), model_labels, model_label_errs, points, neighbors=self.neighbors,
-                             Nneighbors=self.Nneighbors, wt_thresh=wt_thresh, device=self._device)
 
     def predict_phot(self, models, models_err, models_mask, logwt=None):
         """Extension (docs/predictive.md): posterior-predictive photometry ``(phot_mean, phot_var, share)``, each ``(Ndata, Nfilt)``:
         mean and variance of ``scale * model flux`` per band under the rows, the model errors added as the law of total variance,
         masked model bands left out per band (``share``: the weight that was not).  The fitted scales are used when they are kept."""
-        from .pdf import posterior_moments
         if len(models) != self.NMODEL:
             raise ValueError("%d models for fits over %d" % (len(models), self.NMODEL))
-        return posterior_moments(self._rows(logwt), models, models_err, models_mask, scale=self.fit_scale, neighbors=self.neighbors,
-                                 Nneighbors=self.Nneighbors, return_share=True, device=self._device)
+        return self._predict_phot(models, models_err, models_mask, logwt)

@@ -97,6 +97,39 @@ def test_dense_rows(M):
         br.assert_bins(p, br.bins_ref(r6, y6, s6, e), M, below, above)
 
 
+@pytest.mark.parametrize("wpo,W", [(4, 65), (4, 257), (1, 4097)])
+def test_both_geometries_at_the_widths_the_rule_keeps_from_them(wpo, W, monkeypatch):
+    """FZ_DRAW_WPO forces the form the row length would not choose: four waves per object at W = 65 (the object's last two waves own no
+    entry) and 257 (a ragged last pass), with the row that has no entry; one wave per object on the first row too long for it by
+    default.  Masses, below / above and the CDF of each form at the bar that covers both, and per form the same bits for host and
+    device arrays."""
+    if wpo == 4:
+        cases = [br.width_case(W, k) for k in (0, 1)]
+    else:
+        rows, y, s, e = br.dense_case(4097)
+        cases = [(rows, None, None, y, s, e)]
+    eng = engine()
+    dev = lambda a: None if a is None else DevArray(a)
+    monkeypatch.setenv('FZ_DRAW_WPO', str(wpo))
+    for rows, nbr, nnbr, y, s, e in cases:
+        ref = br.bins_ref(rows, y, s, e, nbr, nnbr)
+        assert ref[3] >= (1 if wpo == 4 else 0)
+        p, below, above = bins(rows, y, s, e, nbr, nnbr)
+        br.assert_bins(p, ref, W, below, above)
+        C = cdf(rows, y, s, e, nbr, nnbr)
+        br.assert_close(C, br.cdf_ref(rows, y, s, e, nbr, nnbr)[0], W, "C")
+        N, M, NB = len(rows), len(y), len(e) - 1
+        d_p, d_lo, d_hi, d_c = DevArray(np.zeros((N, NB))), DevArray(np.zeros(N)), DevArray(np.zeros(N)), DevArray(np.zeros((N, NB + 1)))
+        d_rows, d_nbr, d_nn, d_y, d_s = DevArray(rows), dev(nbr), dev(nnbr), DevArray(y), DevArray(s)
+        ns = eng.row_bins(d_rows, N, W, M, d_y, d_s, DevArray(e), NB + 1, d_p, lncut=np.log(1e-3), normalize=False, below=d_lo, above=d_hi,
+                          neighbors=d_nbr, nnbr=d_nn)
+        eng.row_cdf(d_rows, N, W, M, d_y, d_s, DevArray(e), NB + 1, d_c, per_object=False, lncut=np.log(1e-3), neighbors=d_nbr, nnbr=d_nn)
+        assert ns == ref[3]
+        for d, h in ((d_p, p), (d_lo, below), (d_hi, above), (d_c, C)):
+            np.testing.assert_array_equal(dev_numpy(d, h.shape), h)
+    monkeypatch.delenv('FZ_DRAW_WPO')
+
+
 # ---- hand rows -------------------------------------------------------------------------------------------------------------------
 def test_point_masses_on_edges_inside_and_at_the_last_edge():
     e = np.array([0., 1., 2., 4.])

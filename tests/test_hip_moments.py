@@ -120,6 +120,36 @@ def test_dense_rows(M):
         mr.assert_moments(mean, var, mr.moments_ref(*dense_case(4096)), M, share)
 
 
+@pytest.mark.parametrize("wpo,W", [(4, 65), (4, 257), (1, 4097)])
+def test_both_geometries_at_the_widths_the_rule_keeps_from_them(wpo, W, monkeypatch):
+    """FZ_DRAW_WPO forces the form the row length would not choose: four waves per object at W = 65 (the object's last two waves own no
+    entry) and 257 (a ragged last pass), with the row that has no entry; one wave per object on the first row too long for it by
+    default.  Each form at the bar that covers both, and per form the same bits for host and device arrays."""
+    if wpo == 4:
+        cases = []
+        for k, M in enumerate((7, 1000)):
+            rows, nbr, nnbr, sc, V, Ve, Vm = sparse_case(5, W, M, 5, k)
+            cases.append((rows, V, Ve, Vm, sc, nbr, nnbr))
+    else:
+        cases = [dense_case(4097) + (None, None, None)]
+    eng = engine()
+    monkeypatch.setenv('FZ_DRAW_WPO', str(wpo))
+    for rows, V, Ve, Vm, sc, nbr, nnbr in cases:
+        ref = mr.moments_ref(rows, V, Ve, Vm, sc, nbr, nnbr)
+        mean, var, share, ns = raw(rows, V, Ve, Vm, sc, nbr, nnbr)
+        assert ns == ref[3] and ns >= (1 if wpo == 4 else 0)
+        mr.assert_moments(mean, var, ref, W, share)
+        N, M, L = len(rows), len(V), V.shape[1]
+        d_out = [DevArray(np.zeros((N, L))) for _ in range(3)]
+        dev = lambda a: None if a is None else DevArray(a)
+        dns = eng.row_moments(DevArray(rows), N, W, M, L, DevArray(V), d_out[0], var=d_out[1], share=d_out[2], value_errs=DevArray(Ve),
+                              value_mask=DevArray(Vm), scale=dev(sc), neighbors=dev(nbr), nnbr=dev(nnbr))
+        assert dns == ns
+        for d, h in zip(d_out, (mean, var, share)):
+            np.testing.assert_array_equal(dr_numpy(d, (N, L)), h)
+    monkeypatch.delenv('FZ_DRAW_WPO')
+
+
 # ---- row kinds -------------------------------------------------------------------------------------------------------------------
 def test_hand_rows_and_rows_without_a_posterior():
     rows, _ = dr.hand_rows(513, 1, 37)
