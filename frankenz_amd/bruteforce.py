@@ -474,7 +474,7 @@ class BruteForce(RowConsumers):
         return (idx, (lmap, levid)) if return_gof else idx
 
     # ------------------------------------------------------------------
-    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_phot: rows.RowConsumers, over the stored dense
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_quantiles, predict_phot: rows.RowConsumers, over the stored dense
     # (Ndata, Nmodel) rows or given ones
     def _row_source(self, logwt, shaped=False, use_scale=False):
         if logwt is None:

@@ -427,6 +427,14 @@ class Engine(object):
                                   ptr(points), int(P), int(bool(per_object)), float(lncut), ptr(cdf), ptr(ns)))
         return int(ns[0])
 
+    def row_quantiles(self, rows, n, W, M, labels, label_errs, probs, Q, out, lncut=-np.inf, neighbors=None, nnbr=None):
+        """fz_row_quantiles (docs/quantiles.md): the quantiles of every row's mixture CDF at the ``Q`` shared probabilities ``probs`` ->
+        ``out`` (n, Q); returns (rows without a posterior, solves that ended on the evaluation cap, evaluations in all)"""
+        cnt = np.zeros(3, dtype=np.int64)
+        check(self.lib.fz_row_quantiles(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(labels), ptr(label_errs),
+                                        ptr(probs), int(Q), float(lncut), ptr(out), ptr(cnt[0:1]), ptr(cnt[1:2]), ptr(cnt[2:3])))
+        return int(cnt[0]), int(cnt[1]), int(cnt[2])
+
     def phot_sums(self, x, xe, xm, mean, var, n, B, clip=0.):
         """fz_phot_sums -> (sums (3, B) float64 = A, B, C; counts (2, B) int64 = n, nclip)"""
         sums, counts = np.zeros((3, int(B))), np.zeros((2, int(B)), dtype=np.int64)

@@ -598,7 +598,7 @@ class NearestNeighbors(RowConsumers):
             raise ValueError("`logwt` has shape %s; expected (Ndata, K*k) = (%d, %d) like `neighbors`" % (lw.shape, Ndata, W))
         return RowConsumers._draw_rows(self, lw, nb, nn, S, u, key)
 
-    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_phot: rows.RowConsumers, over the stored padded
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_quantiles, predict_phot: rows.RowConsumers, over the stored padded
     # (Ndata, K*k) rows beside ``neighbors`` / ``Nneighbors``, or given rows of that layout
     def _draw_rows(self, lw, neighbors, Nneighbors, S, u, key):
         return self._draw_stored(lw, S, u, key)

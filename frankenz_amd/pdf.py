@@ -18,7 +18,7 @@ from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
            "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt", "posterior_moments",
-           "gaussian_bin", "posterior_bins", "posterior_cdf", "BINS_MAX"]
+           "gaussian_bin", "posterior_bins", "posterior_cdf", "posterior_quantiles", "BINS_MAX"]
 
 BINS_MAX = 256       # FZ_BINS_MAX: bins of a posterior_bins call, points of a posterior_cdf call
 
@@ -395,6 +395,48 @@ def posterior_cdf(logwt, labels, label_errs, points, neighbors=None, Nneighbors=
     cdf = np.full((N, P), np.nan)
     get_engine(device).row_cdf(lw, N, W, M, y, s, x, P, cdf, per_object=per_object, lncut=lncut, neighbors=nb, nnbr=nn)
     return cdf[:, 0] if pit else cdf
+
+
+def posterior_quantiles(logwt, labels, label_errs, q, neighbors=None, Nneighbors=None, wt_thresh=1e-3, out=None, return_info=False,
+                        device=None):
+    """Quantiles of the mixture ``posterior_cdf`` inverts, without a grid (extension; docs/quantiles.md states the law): per row
+    ``Q(p) = inf{x : C(x) >= p}`` under the selection and normalisation of ``posterior_bins``, found by a safeguarded Newton on the
+    device to the resolution of float64 in ``C`` and in ``x``.  ``q``: the probabilities, each strictly inside (0, 1), shared by all
+    objects, in any order, at most 256; a scalar gives ``(Ndata,)``, otherwise ``(Ndata, Q)``.  ``label_errs`` must be finite
+    (``posterior_bins`` accepts ``inf``; a flat kernel has no quantile), 0 is a point mass.  ``out``: a C-contiguous float64
+    ``(Ndata, Q)`` NumPy or device array, filled in place and returned.  ``return_info`` adds a dict with ``nskip`` (rows without a
+    posterior: nan), ``nfail`` (solves that ended on the cap of 128 evaluations and returned their bracket midpoint; also a
+    ``RuntimeWarning``) and ``niter`` (evaluations of the CDF in all)."""
+    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+    one = not hasattr(q, "data_ptr") and np.ndim(q) == 0
+    p = _rows_arg(np.atleast_1d(q) if not hasattr(q, "data_ptr") else q, np.float64, "q")
+    if len(p.shape) != 1 or int(p.shape[0]) < 1:
+        raise ValueError("`q` must be a scalar or a 1-D array of at least one probability")
+    Q = int(p.shape[0])
+    if Q > BINS_MAX:
+        raise NotImplementedError("%d probabilities, the limit is %d (FZ_BINS_MAX)" % (Q, BINS_MAX))
+    if isinstance(p, np.ndarray) and not ((p > 0.) & (p < 1.)).all():
+        raise ValueError("`q` must lie strictly inside (0, 1)")
+    if isinstance(y, np.ndarray) and not np.isfinite(y).all():
+        raise ValueError("`labels` must be finite")
+    if isinstance(s, np.ndarray) and not (np.isfinite(s) & (s >= 0.)).all():
+        raise ValueError("`label_errs` must be finite and not negative (a flat kernel, inf, has no quantile)")
+    if isinstance(y, np.ndarray) and isinstance(s, np.ndarray):
+        with np.errstate(over='ignore'):
+            bad = ~np.isfinite(np.abs(y) + 40. * s)
+        if bad.any():
+            raise ValueError("model %d: |label| + 40 label_err overflows" % int(np.argmax(bad)))
+    if out is None:
+        out = np.full((N, Q), np.nan)
+    elif tuple(out.shape) != (N, Q) or _rows_arg(out, np.float64, "out") is not out:
+        raise ValueError("`out` must be a C-contiguous float64 array of shape (Ndata, Q) = (%d, %d)" % (N, Q))
+    nskip, nfail, niter = get_engine(device).row_quantiles(lw, N, W, M, y, s, p, Q, out, lncut=lncut, neighbors=nb, nnbr=nn)
+    if nfail:
+        import warnings
+        warnings.warn("posterior_quantiles: %d solves ended on the cap of 128 evaluations and return their bracket midpoint" % nfail,
+                      RuntimeWarning, stacklevel=2)
+    res = out[:, 0] if (one and isinstance(out, np.ndarray)) else out
+    return (res, dict(nskip=nskip, nfail=nfail, niter=niter)) if return_info else res
 
 
 class PDFDict(object):

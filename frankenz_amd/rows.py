@@ -1,6 +1,6 @@
 """
 ``RowConsumers`` -- the methods that ``BruteForce``, ``NearestNeighbors`` and ``SparseFits`` share: everything that consumes rows of
-ln-weights after a fit (posterior draws, the model-weight samplers, moments, bin masses, CDFs, predictive photometry).  The fitters
+ln-weights after a fit (posterior draws, the model-weight samplers, moments, bin masses, CDFs, quantiles, predictive photometry).  The fitters
 differ in where the rows come from, in whether they come with ``neighbors`` / ``Nneighbors``, and in what they say when there are
 none; each says so in two hooks:
 
@@ -91,6 +91,15 @@ class RowConsumers(object):
         lw, nb, nn = self._row_source(logwt)
         return posterior_cdf(lw, model_labels, model_label_errs, points, neighbors=nb, Nneighbors=nn, wt_thresh=wt_thresh,
                              device=self._device)
+
+    def predict_quantiles(self, model_labels, model_label_errs, q=(0.025, 0.16, 0.5, 0.84, 0.975), logwt=None, wt_thresh=1e-3, out=None):
+        """Extension (docs/quantiles.md): the quantiles of that mixture CDF at the probabilities ``q`` (``pdf.posterior_quantiles``):
+        by default the median and the 68 % and 95 % credible intervals of the label per object, ``(Ndata, 5)``, without a grid."""
+        from .pdf import posterior_quantiles
+        self._check_labels(model_labels)
+        lw, nb, nn = self._row_source(logwt)
+        return posterior_quantiles(lw, model_labels, model_label_errs, q, neighbors=nb, Nneighbors=nn, wt_thresh=wt_thresh, out=out,
+                                   device=self._device)
 
     def _predict_phot(self, models, models_err, models_mask, logwt):
         from .pdf import posterior_moments

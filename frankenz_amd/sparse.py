@@ -85,7 +85,7 @@ class SparseFits(RowConsumers):
             sys.stderr.flush()
         return (pdfs, (lmap, levid)) if return_gof else pdfs
 
-    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf: rows.RowConsumers, over the sparse rows
+    # sample, weight_sampler, weight_em, moments, predict_bins, predict_cdf, predict_quantiles: rows.RowConsumers, over the sparse rows
     def _row_source(self, logwt, shaped=False, use_scale=False):
         if use_scale and self.fit_scale is None:
             raise ValueError("the scale rows were not kept (`track_scale=True`)")

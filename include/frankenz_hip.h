@@ -657,6 +657,41 @@ int  fz_row_cdf(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int
                 const double* labels, const double* label_errs, const double* points, int64_t P, int32_t per_object, double lncut,
                 double* cdf, int64_t* nskip);
 
+/* ---- posterior quantiles of the same label kernel (extension, no reference counterpart; docs/quantiles.md) ----
+ * The law.  Selection, w_t, Z, the strict ln-space cut and the rows without a posterior (every output nan, counted in nskip) are
+ * those of fz_row_cdf; entries past nnbr[i] are never read.  C(x) = sum w_t F_t(x) / Z with F_t the right-continuous kernel CDF
+ * above, C-(x) its left limit (x > y_j for s_j == 0), and the quantile function is Q(p) = inf{x : C(x) >= p}.  probs[0..Q): each
+ * finite and strictly inside (0, 1), shared by all objects, in any order, duplicates allowed, 1 <= Q <= 256 (FZ_BINS_MAX).  Label
+ * errors must be finite here (s = inf has no quantile) and |y_j| + 40 s_j must be finite.  Per row, over the included entries:
+ *     hull   [a0, b0] = [min(y_j - 40 s_j), max(y_j + 40 s_j)]   (erfc(40 / sqrt 2) is 0 in fp64: C(a0-) = 0, C(b0) = 1 as evaluated)
+ *     R = max(|a0|, |b0|),  delta = 4 u R,  tau = 4 (W / 64 + 16) u,  u = 2^-53
+ * An output x for (row, p) lies in the hull and satisfies, in exact arithmetic,
+ *     C-(x - 2 delta) - 2 tau  <=  p  <=  C(x + 2 delta) + 2 tau
+ * -- |C(x) - p| <= 2 tau up to 2 delta on a continuous mixture, within 2 delta of the label at which C crosses p at a point mass, any
+ * point of the gap on a flat stretch.  The solve keeps a bracket C_dev(a) < p <= C_dev(b) from the hull inward and stops at
+ * |C_dev(x) - p| <= tau with a positive density sum at x (x is returned) or b - a <= delta (b is returned); C_dev is the fixed-order
+ * sum of fz_row_cdf, within tau of C.  Where the density sum is 0 (point masses, a gap) the solve goes on to the lower end of the flat
+ * stretch: p = 1/2 of two equal point masses gives the lower label.
+ * Each evaluation also forms the density sum w_t q_j exp(-z^2) / sqrt(pi), z = (x - y_j) q_j (0 for s_j == 0).  The step is Newton's from
+ * the bracket end with the smaller residual, and a bisection when that end's density is 0, when the Newton point leaves the bracket,
+ * or when neither the bracket nor that residual halved in the last step; the first bisections go to the ends of Cantelli's bracket
+ * mu -+ sigma sqrt((1 - p) / p), sqrt(p / (1 - p)) (mixture mean and deviation, rounded outward, inside the hull), later ones to the
+ * midpoint.  The start is mu + 0.6267 sigma ln(p / (1 - p)) inside that bracket.  At most FZ_QUANT_MAXIT = 128 evaluations per
+ * (row, p): a solve that ends on the cap returns its bracket midpoint and is counted in nfail; niter is the total number of
+ * evaluations.  An output is a function of the row's counted entries in order, the label records, p and W alone: not of the other
+ * probabilities, their number or order, the chunking under the workspace limit, the object order or count, or host versus device
+ * arguments.
+ * Refusals, before any row is walked: Q < 1, a probability outside (0, 1) or not finite, a label that is not finite, an error that is
+ * negative, nan or inf, an overflowing |y| + 40 s (the smallest such model is named), lncut >= 0 or nan: -4; Q > 256 (FZ_BINS_MAX),
+ * W > 2^20 (FZ_DRAW_LMAX) or M >= 2^31: -5.  An index outside [0, M) within the count, or a count outside [0, W]: -3, before anything
+ * is gathered for that row.
+ *
+ * fz_row_quantiles -- rows, neighbors, nnbr as fz_row_bins; labels, label_errs (M), probs (Q): host or device; out (N, Q): host or
+ *   device, staged in chunks; nskip, nfail, niter: one int64 each, host or device. */
+int  fz_row_quantiles(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                      const double* labels, const double* label_errs, const double* probs, int64_t Q, double lncut, double* out,
+                      int64_t* nskip, int64_t* nfail, int64_t* niter);
+
 /* ---- Monte-Carlo draws of the k-NN fitter on the device (extension; docs/knn.md, knn.py:158-188 / 830-832) ----
  * The reference draws its K feature sets (knn.py:158-188) and every object's query features (knn.py:830-832) with NumPy's normal and
  * maps them to magnitudes / luptitudes.  Here the variates are Philox4x32-10: one call gives two standard normals by Box-Muller
