@@ -112,6 +112,7 @@ ABI = {
     "fz_nz_sweep": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, C.c_uint32, C.c_uint32, C.c_uint64, _P]),
     "fz_net_select": (C.c_int, [_P, _P, _I64, _I32, _I32, _F64, _F64, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "fz_net_table": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _I64, _P]),
+    "fz_net_union": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _I64, _I64, _P, _P]),
     "fz_net_gather": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, C.c_uint64, _P]),
     "fz_net_stack": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I64, _I64, _P, _P, _P]),
     "fz_som_train": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I64, _I32, _I32, _F64, _F64,

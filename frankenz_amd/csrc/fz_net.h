@@ -3,6 +3,7 @@
 // 1413-1473.  One wave per object; the object's row of node ln-probabilities sits in LDS.
 #pragma once
 #include "fz_device.h"
+#include "fz_grid.h"
 
 namespace fz {
 
@@ -123,6 +124,126 @@ __global__ __launch_bounds__(256) void k_net_table(const int32_t* __restrict__ n
         pos += b - a;
     }
     for (int64_t k = pos + lane; k < W; k += 64) out[k] = first;
+}
+
+// ---- the union of the selected nodes' lists, repeats removed, ascending (fz_net_union; docs/network.md, "Sparse rows") ----
+// (FZ_NET_UNION_MMAX = 2^20 models, include/frankenz_hip.h: a wave's bitmap of M bits is then 128 KB of the 160 KB of LDS)
+
+// Waves (= objects) per block of k_net_union: four while four bitmaps of ceil(M / 32) words fit in LDS, then two, then one
+__host__ __device__ inline size_t fz_net_union_words(int64_t M) { return (size_t)((M + 31) / 32); }
+inline int fz_net_union_waves(int64_t M) {
+    const size_t bytes = fz_net_union_words(M) * 4;
+    return bytes * 4 <= FZ_LDS_BYTES ? 4 : bytes * 2 <= FZ_LDS_BYTES ? 2 : 1;
+}
+
+// Before any row is written: which nodes some object's selection reaches (reached[nd] = 1; every writer stores the same value), a
+// column or node index outside its table (flag bit 2) ...  A wave per object, lanes along its selection.
+__global__ __launch_bounds__(256) void k_net_reach(const int32_t* __restrict__ nsel, const int32_t* __restrict__ sel, int64_t N, int Nn,
+                                                   const int32_t* __restrict__ match, int64_t Nnodes, int32_t* __restrict__ reached,
+                                                   int32_t* __restrict__ flag) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const int n = nsel[i];
+    if (n < 0 || n > Nn) { if (lane == 0) atomicOr(flag, 2); return; }
+    bool bad = false;
+    for (int s = lane; s < n; s += 64) {
+        const int c = sel[i * Nn + s];
+        if (c < 0 || c >= Nn) { bad = true; continue; }
+        const int64_t nd = match ? match[c] : c;
+        if (nd < 0 || nd >= Nnodes) { bad = true; continue; }
+        reached[nd] = 1;
+    }
+    if (__any(bad) && lane == 0) atomicOr(flag, 2);
+}
+// ... and a model index outside [0, M) in the list of a reached node (flag bit 1); lists that run backwards or past the items
+// (flag bit 2).  A wave per node.
+__global__ __launch_bounds__(256) void k_net_check(const int32_t* __restrict__ reached, int64_t Nnodes, const int64_t* __restrict__ csr_off,
+                                                   const int64_t* __restrict__ csr_items, int64_t nitems, int64_t M, int32_t* __restrict__ flag) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nd = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (nd >= Nnodes || !reached[nd]) return;
+    const int64_t a = csr_off[nd], b = csr_off[nd + 1];
+    if (a < 0 || b < a || b > nitems) { if (lane == 0) atomicOr(flag, 2); return; }
+    bool bad = false;
+    for (int64_t k = a + lane; k < b; k += 64) { const int64_t v = csr_items[k]; bad |= v < 0 || v >= M; }
+    if (__any(bad) && lane == 0) atomicOr(flag, 1);
+}
+
+// U_i = the set of model indices in the lists of object i's selected nodes: nuniq[i] = |U_i| and, EMIT, idx[i][0 .. W) = its elements
+// ascending, cut at W, padded with the smallest (the table fz_knn_fit_predict takes; an empty union: W times index 0, as k_net_table).
+// One wave per object and a bitmap of M bits per wave in LDS.  The bitmap is cleared WHOLE, once: a wave has one object, the LDS of a
+// fresh block holds anything, and the emit pass reads every word anyway -- clearing only the touched words would read the lists a
+// second time from global memory to save, at most, as many LDS stores as the emit pass issues loads.  Lanes stride over each list
+// and set bits with the integer LDS atomic OR (order-free: the bitmap, and so every output, is deterministic).  The emit pass walks
+// the words in order, 64 a step: a lane's count is the popcount of its word, the wave prefix of the counts comes from one ballot /
+// mbcnt pair per bit of the count (0 .. 32: six), and each lane writes its word's set bits ascending from its prefix.
+// fz_net_union has validated every index the selection reaches (k_net_reach, k_net_check); the guards below only keep a stray index
+// from touching memory.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_net_union(const int32_t* __restrict__ nsel, const int32_t* __restrict__ sel, int64_t N, int Nn,
+                                                   const int32_t* __restrict__ match, const int64_t* __restrict__ csr_off,
+                                                   const int64_t* __restrict__ csr_items, int64_t M, int64_t W, int64_t* __restrict__ nuniq,
+                                                   int64_t* __restrict__ idx) {
+    extern __shared__ uint32_t s_union[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (i >= N) return;
+    const int words = (int)fz_net_union_words(M);
+    uint32_t* bm = s_union + (size_t)wave * words;
+    for (int w = lane; w < words; w += 64) bm[w] = 0u;
+    // (the wave's own LDS operations complete in order; the fences keep the compiler from moving them across the phases)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int n = nsel[i];
+    // (the bounds of 64 lists at a time, a lane each, then handed round the wave: one load in front of a list's items, not four)
+    for (int s0 = 0; s0 < n; s0 += 64) {
+        long long a = 0, b = 0;
+        if (s0 + lane < n) {
+            const int c = sel[i * Nn + s0 + lane];
+            const int nd = match ? match[c] : c;
+            a = csr_off[nd]; b = csr_off[nd + 1];
+        }
+        const int m = n - s0 < 64 ? n - s0 : 64;
+        for (int t = 0; t < m; ++t) {
+            const long long ta = __shfl(a, t, 64), tb = __shfl(b, t, 64);
+            for (long long k = ta + lane; k < tb; k += 64) {
+                const int64_t v = csr_items[k];
+                if (v >= 0 && v < M) atomicOr(&bm[v >> 5], 1u << (v & 31));
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int64_t* out = EMIT ? idx + i * W : nullptr;
+    int64_t pos = 0, first = 0;                                     // wave-uniform: entries so far, the smallest element
+    for (int w0 = 0; w0 < words; w0 += 64) {
+        const int w = w0 + lane;
+        uint32_t bits = w < words ? bm[w] : 0u;
+        const unsigned long long any = __ballot(bits != 0u);
+        if (!any) continue;
+        const int cnt = __popc(bits);
+        int pre = 0, tot = 0;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            const unsigned long long m = __ballot((cnt >> b) & 1);
+            pre += __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0)) << b;
+            tot += __builtin_popcountll(m) << b;
+        }
+        if (EMIT) {
+            if (pos == 0) {                                           // the first word that holds a bit: its lowest bit is the smallest element
+                const int l0 = __builtin_ctzll(any);
+                first = (int64_t)(w0 + l0) * 32 + __builtin_ctz(__shfl(bits, l0, 64));
+            }
+            int64_t p = pos + pre;
+            while (bits) {
+                if (p < W) out[p] = (int64_t)w * 32 + __builtin_ctz(bits);
+                ++p;
+                bits &= bits - 1;
+            }
+        }
+        pos += tot;
+    }
+    if (lane == 0) nuniq[i] = pos;
+    if (EMIT) for (int64_t k = pos + lane; k < W; k += 64) out[k] = first;
 }
 
 // out[i][s] = plane[i][sel[i][s]] for s < nsel[i], pad beyond (8-byte elements: the node results of nodes_only fits, networks.py:907-909)

@@ -58,6 +58,59 @@ extern "C" int fz_net_table(fz_ctx* c, const int32_t* nsel, const int32_t* sel, 
     return 0;
 }
 
+extern "C" int fz_net_union(fz_ctx* c, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, const int32_t* match,
+                            const int64_t* csr_off, const int64_t* csr_items, int64_t Nnodes, int64_t M, int64_t W, int64_t* nuniq, int64_t* idx) {
+    if (!c || !nsel || !sel || !csr_off || !csr_items || !nuniq) return fail(-1, "fz_net_union: NULL argument");
+    if (M < 1 || Nn < 1 || Nnodes < 1) return fail(-4, "fz_net_union: %lld models, %d columns, %lld nodes", (long long)M, Nn, (long long)Nnodes);
+    if (M > FZ_NET_UNION_MMAX)
+        return fail(-5, "fz_net_union: %lld models exceed FZ_NET_UNION_MMAX = %d (an object's bitmap of M bits sits in LDS)", (long long)M, FZ_NET_UNION_MMAX);
+    if (idx && W < 1) return fail(-4, "fz_net_union: a table of width %lld", (long long)W);
+    if (N <= 0) return 0;
+    if (N >= ((int64_t)1 << 31)) return fail(-5, "fz_net_union: %lld objects in one call", (long long)N);
+    HIPCHK(hipSetDevice(c->device));
+    FZCHK(wait_for_producers(c, {nsel, sel, match, csr_off, csr_items, nuniq, idx}));
+    StageWhole st{c};
+    const void *d_nsel, *d_sel, *d_match, *d_off, *d_items; void *d_nu, *d_idx, *d_reach;
+    int64_t nitems = 0;
+    FZCHK(host_read(&nitems, csr_off + Nnodes, 8));
+    if (nitems < 0) return fail(-4, "fz_net_union: the node lists end at %lld", (long long)nitems);
+    FZCHK(st.in(nsel, (size_t)N * 4, &d_nsel)); FZCHK(st.in(sel, (size_t)N * Nn * 4, &d_sel)); FZCHK(st.in(match, (size_t)Nn * 4, &d_match));
+    FZCHK(st.in(csr_off, (size_t)(Nnodes + 1) * 8, &d_off)); FZCHK(st.in(csr_items, (size_t)nitems * 8, &d_items));
+    FZCHK(st.out(nuniq, (size_t)N * 8, &d_nu));
+    FZCHK(st.out(idx, idx ? (size_t)N * W * 8 : 0, &d_idx));
+    FZCHK(st.slot((size_t)Nnodes * 4, &d_reach));
+    // every index the selection reaches is checked before a row is written: the nodes some object selects, then their lists
+    HIPCHK(hipMemsetAsync(d_reach, 0, (size_t)Nnodes * 4, c->stream));
+    int ef = 0;
+    FZCHK(fz_flag_roundtrip(c, ef, [&](int* d_flags) {
+        Timer t(c, &c->tm.ms_other, &c->tm.n_other);
+        hipLaunchKernelGGL(fz::k_net_reach, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, (const int32_t*)d_nsel, (const int32_t*)d_sel, N,
+                           (int)Nn, (const int32_t*)d_match, Nnodes, (int32_t*)d_reach, (int32_t*)d_flags);
+        hipLaunchKernelGGL(fz::k_net_check, dim3((unsigned)((Nnodes + 3) / 4)), dim3(256), 0, c->stream, (const int32_t*)d_reach, Nnodes,
+                           (const int64_t*)d_off, (const int64_t*)d_items, nitems, M, (int32_t*)d_flags);
+        return 0;
+    }));
+    if (ef & 2) return fail(-3, "fz_net_union: the selection, `match` or the lists' offsets point outside their tables");
+    if (ef & 1) return fail(-3, "fz_net_union: a list that a selected node reaches holds a model index outside [0, %lld)", (long long)M);
+    // a wave per object, a bitmap of ceil(M / 32) words each: four waves a block while four bitmaps fit in LDS, then two, then one
+    const int waves = fz::fz_net_union_waves(M);
+    const size_t lds = (size_t)waves * fz::fz_net_union_words(M) * 4;
+    const void* kern = idx ? (const void*)fz::k_net_union<true> : (const void*)fz::k_net_union<false>;
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    {
+        Timer t(c, &c->tm.ms_other, &c->tm.n_other);
+        const dim3 grid((unsigned)((N + waves - 1) / waves)), blk(64 * waves);
+        if (idx) hipLaunchKernelGGL(fz::k_net_union<true>, grid, blk, lds, c->stream, (const int32_t*)d_nsel, (const int32_t*)d_sel, N, (int)Nn,
+                                    (const int32_t*)d_match, (const int64_t*)d_off, (const int64_t*)d_items, M, W, (int64_t*)d_nu, (int64_t*)d_idx);
+        else hipLaunchKernelGGL(fz::k_net_union<false>, grid, blk, lds, c->stream, (const int32_t*)d_nsel, (const int32_t*)d_sel, N, (int)Nn,
+                                (const int32_t*)d_match, (const int64_t*)d_off, (const int64_t*)d_items, M, (int64_t)0, (int64_t*)d_nu, (int64_t*)nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    FZCHK(st.finish());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 extern "C" int fz_net_gather(fz_ctx* c, const void* plane, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, int32_t W,
                              uint64_t pad_bits, void* out) {
     if (!c || !plane || !nsel || !sel || !out) return fail(-1, "fz_net_gather: NULL argument");

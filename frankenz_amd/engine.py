@@ -514,6 +514,15 @@ class Engine(object):
         check(self.lib.fz_net_table(self.h, ptr(nsel), ptr(sel), n, nn, ptr(match), ptr(csr_off), ptr(csr_items), len(csr_off) - 1,
                                     int(W), ptr(idx)))
 
+    def net_union(self, nsel, sel, match, csr_off, csr_items, M, nuniq, W=0, idx=None, n=None, nn=None):
+        """fz_net_union: per object the union of its selected nodes' lists, repeats removed -> ``nuniq`` (n) int64 and, with ``idx``
+        (n, W) int64, its elements ascending, padded with the smallest (``idx`` None: the counting call).  ``n`` / ``nn``: the
+        shape of ``sel`` where it is handed over as a raw pointer"""
+        if n is None:
+            n, nn = sel.shape
+        check(self.lib.fz_net_union(self.h, ptr(nsel), ptr(sel), int(n), int(nn), ptr(match), ptr(csr_off), ptr(csr_items),
+                                    len(csr_off) - 1, int(M), int(W), ptr(nuniq), ptr(idx)))
+
     def net_gather(self, plane, nsel, sel, W, pad, out):
         n, nn = sel.shape
         bits = int(np.array([pad], dtype=plane.dtype).view(np.uint64)[0])
@@ -609,6 +618,10 @@ class Engine(object):
         d = DeviceArray(self, a.shape, a.dtype)
         d.set_rows(0, a)
         return d
+
+    def dev_copy(self, dst, src, nbytes):
+        """fz_dev_copy: ``nbytes`` from ``src`` to ``dst``, each a NumPy array, a device array or a raw address of either kind"""
+        check(self.lib.fz_dev_copy(self.h, ptr(dst), ptr(src), int(nbytes)))
 
     def pdfs_colsum(self, pdfs, G, out, n=None):
         n = len(pdfs) if n is None else n

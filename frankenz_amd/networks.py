@@ -13,6 +13,8 @@ through the library:
   PDFs) or the union of the selected nodes' model lists (``fz_net_table``) through the k-NN subset kernel (``fz_knn_fit_predict``:
   first-appearance de-dup = pandas.unique, likelihood, weights, KDE).
 * ``get_pdfs`` (networks.py:413-560): per-node KDE of the member models (``fz_knn_predict_logwt``), scaled by exp(levid).
+* ``fit_sparse`` (extension, docs/network.md "Sparse rows"): the fit as a ``SparseFits`` over the union of the selected nodes' lists
+  with repeats removed on the device (``fz_net_union``), sized by the largest union instead of the summed list lengths.
 
 A foreign ``lpnet_func`` / ``lprob_func`` is the user's code: it is called on the host per object exactly as the reference calls it;
 the selection, the unions and the PDFs still run on the device.
@@ -30,6 +32,7 @@ __all__ = ["populate_network", "Network", "SelfOrganizingMap", "GrowingNeuralGas
 _NET_CHUNK = 1 << 16          # objects per device call
 _NODES_MAX = 4096             # matched nodes fz_net_select takes (an object's row sits in LDS)
 _UNION_MAX = 4096             # entries of an object's union table before de-duplication (FZ_KNN_WMAX)
+_UNION_MMAX = 1 << 20         # models fz_net_union takes (FZ_NET_UNION_MMAX: an object's bitmap of the models sits in LDS)
 
 
 class NetworkMap(object):
@@ -427,6 +430,144 @@ class Network(object):
         for r in self._run(data, data_err, data_mask, lprob_func, nodes_only, wt_thresh, cdf_thresh, lprob_args, lprob_kwargs,
                            track_scale, discrete, save_fits):
             yield r
+
+    # -- extension: the fit as sparse rows (docs/network.md, "Sparse rows") ---------------------------------------------------
+    def fit_sparse(self, data, data_err, data_mask, lprob_func=None, wt_thresh=1e-3, cdf_thresh=2e-4, lprob_args=None,
+                   lprob_kwargs=None, track_scale=False, discrete=False, resident=False, verbose=True):
+        """Extension (no reference counterpart; docs/network.md, "Sparse rows"): the fit of ``fit`` -- the same selection of nodes,
+        the built-in likelihood of every object against the models its selected nodes list -- left as a ``SparseFits`` in the layout
+        ``NearestNeighbors.fit`` leaves, so that ``predict`` / ``sample`` / ``weight_sampler`` / ``weight_em`` / ``moments`` /
+        ``predict_bins`` / ``predict_cdf`` / ``predict_quantiles`` / ``predict_phot`` run on a fit through the network.  The
+        candidate set of an object is the union of its nodes' lists with repeats removed (``fz_net_union``), and the width of the
+        rows is the largest such union of the call (at most ``FZ_KNN_WMAX``), not the summed list length ``fit`` is sized by.
+        ``neighbors`` holds each row's model indices in ASCENDING order, padded -99 (column 0 is the smallest index, not the MAP
+        model); ``lmap`` / ``levid`` are the max / logsumexp of the row and ``cover()`` is 1.  There is no ``nodes_only``.  No
+        attribute of this object is touched; the in-place clean of the objects reaches the caller's arrays.  ``resident=True``
+        leaves ``neighbors``, ``Nneighbors``, ``fit_lnlike`` and ``fit_lnprob`` as device arrays of the engine (the other ``fit_*``
+        are then None)."""
+        from .sparse import SparseFits
+        if self.nodes_idxs is None:
+            raise ValueError("Network has not been trained!")
+        if not (_is_default(lprob_func) and not lprob_args):
+            raise NotImplementedError("fit_sparse needs the built-in likelihood (a foreign `lprob_func` returns rows of its own "
+                                      "layout: use `fit`)")
+        if not (_is_default(getattr(self, 'lpnet_func', None)) and not getattr(self, 'lpnet_args', None)):
+            raise NotImplementedError("fit_sparse needs a network populated with the built-in node likelihood (`lpnet_func`)")
+        if self.NMODEL > _UNION_MMAX:
+            raise NotImplementedError("%d models exceed FZ_NET_UNION_MMAX = %d (an object's bitmap of the models sits in LDS)"
+                                      % (self.NMODEL, _UNION_MMAX))
+        opts = like_opts(lprob_kwargs)
+        nopts = like_opts(self.lpnet_kwargs)
+        if wt_thresh is None and cdf_thresh is None:
+            wt_thresh = -np.inf
+        use_wt = wt_thresh is not None
+        sel_args = (use_wt, wt_thresh if use_wt else 0.0, 0.5 if use_wt or cdf_thresh is None else cdf_thresh)
+        eng = self._eng()
+        Ndata, M = len(data), self.NMODEL
+        match_sel = np.arange(self.NNODE)[self.nodes_Nmatch > 0]
+        match32 = np.ascontiguousarray(match_sel, dtype=np.int32)
+        y = np.ascontiguousarray(self.nodes[match_sel]); Nn = len(y)
+        off, items = _csr(self.nodes_bmus if discrete else self.nodes_idxs)
+        d_match, d_off, d_items = eng.device_array(match32), eng.device_array(off), eng.device_array(items)
+        # Objects per device call: the (n, Nn) node plane, sel (n, Nn) int32, nsel and the counts inside a quarter of the workspace
+        # budget.  The selection of the counting pass stays on the device for the fitting pass while all of it fits another quarter;
+        # otherwise the fitting pass forms it again, chunk by chunk.
+        limit = eng.workspace_limit()
+        sel_row = Nn * 4 + 4
+        keep = Ndata * sel_row <= limit // 4
+        nc1 = int(max(1, min(_NET_CHUNK, (limit // 4) // (Nn * 8 + (0 if keep else sel_row) + 8))))
+
+        def select(i0, n, d_nsel, d_sel):
+            """the node likelihoods of objects [i0, i0 + n) (cleaned in place, written back) and their selection, on the device"""
+            obj = HostObjects(data[i0:i0 + n], data_err[i0:i0 + n], data_mask[i0:i0 + n])
+            plane = eng.device_empty((n, Nn), np.float64)
+            eng.upload_models(y, np.zeros_like(y), np.ones_like(y))
+            eng.fit(obj.x, obj.xe, obj.xm, nopts, plane, n=n)
+            obj.writeback()
+            eng.net_select(plane, *sel_args, None, None, d_nsel, d_sel)
+            return obj
+
+        # ---- pass 1: the selections and the sizes of the unions; every refusal falls here, before the first subset fit ----
+        nuniq = np.zeros(Ndata, dtype=np.int64)
+        if keep and Ndata:
+            all_nsel, all_sel = eng.device_empty((Ndata,), np.int32), eng.device_empty((Ndata, Nn), np.int32)
+        for i0 in range(0, Ndata, nc1):
+            n = min(nc1, Ndata - i0)
+            if keep:
+                d_nsel, d_sel = all_nsel.data_ptr() + i0 * 4, all_sel.data_ptr() + i0 * Nn * 4
+                hold = None
+            else:
+                hold = (eng.device_empty((n,), np.int32), eng.device_empty((n, Nn), np.int32))
+                d_nsel, d_sel = hold[0].data_ptr(), hold[1].data_ptr()
+            select(i0, n, d_nsel, d_sel)
+            nsel = np.empty(n, dtype=np.int32)
+            eng.dev_copy(nsel, d_nsel, nsel.nbytes)
+            if not nsel.all():
+                k = int(np.argmin(nsel != 0))
+                raise ValueError("object %d selects no node of the network (%d of %d objects in this call do): its node ln-probabilities "
+                                 "hold a nan, or none passes the threshold (wt_thresh=%r, cdf_thresh=%r)"
+                                 % (i0 + k, int((nsel == 0).sum()), n, wt_thresh, cdf_thresh))
+            eng.net_union(d_nsel, d_sel, d_match, d_off, d_items, M, nuniq[i0:i0 + n], n=n, nn=Nn)
+            if not nuniq[i0:i0 + n].all():
+                raise ValueError("object %d: the nodes it selects list no model" % (i0 + int(np.argmin(nuniq[i0:i0 + n] != 0))))
+        W = max(int(nuniq.max()), 1) if Ndata else 1
+        if W > _UNION_MAX:
+            raise NotImplementedError("object %d: its selected nodes list %d different models; the union table of fz_knn_fit_predict "
+                                      "holds at most FZ_KNN_WMAX = %d" % (int(np.argmax(nuniq)), W, _UNION_MAX))
+
+        # ---- pass 2: the tables and the subset likelihood, straight into rows [i0, i0 + n) of the (Ndata, W) outputs ----
+        free = track_scale and bool(opts.free_scale)
+        if resident:
+            new = lambda dt: eng.device_empty((Ndata, W), dt)
+            nbr, cnt = new(np.int64), eng.device_empty((Ndata,), np.int64)
+            lnl, lpb = new(np.float64), new(np.float64)
+            lpr = chi2 = ndim = sc = se = None
+        else:
+            new = lambda dt: np.empty((Ndata, W), dtype=dt)
+            nbr, cnt = new(np.int64), np.zeros(Ndata, dtype=np.int64)
+            lnl, chi2, ndim = new(np.float64), new(np.float64), new(np.int64)
+            sc, se = (new(np.float64), new(np.float64)) if free else (None, None)
+
+        def rows(a, i0, n, width=W):
+            """rows [i0, i0 + n) of an output: a view of a host array, a raw pointer into a device array"""
+            if a is None:
+                return None
+            return a[i0:i0 + n] if isinstance(a, np.ndarray) else a.data_ptr() + i0 * width * 8
+
+        nc2 = int(max(1, min(_NET_CHUNK, (limit // 4) // (W * 8 + (0 if keep else Nn * 8 + sel_row)))))
+        for i0 in range(0, Ndata, nc2):
+            n = min(nc2, Ndata - i0)
+            if keep:
+                d_nsel, d_sel = all_nsel.data_ptr() + i0 * 4, all_sel.data_ptr() + i0 * Nn * 4
+                obj = HostObjects(data[i0:i0 + n], data_err[i0:i0 + n], data_mask[i0:i0 + n])
+            else:
+                hold = (eng.device_empty((n,), np.int32), eng.device_empty((n, Nn), np.int32))
+                d_nsel, d_sel = hold[0].data_ptr(), hold[1].data_ptr()
+                obj = select(i0, n, d_nsel, d_sel)
+            idx = eng.device_empty((n, W), np.int64)
+            nu = eng.device_empty((n,), np.int64)
+            eng.net_union(d_nsel, d_sel, d_match, d_off, d_items, M, nu, W, idx, n=n, nn=Nn)
+            eng.upload_models(self.models, self.models_err, self.models_mask)
+            eng.knn_fit_predict(obj.x, obj.xe, obj.xm, idx, W, opts, None, rows(nbr, i0, n), rows(cnt, i0, n, 1), rows(lnl, i0, n),
+                                rows(chi2, i0, n), rows(ndim, i0, n), rows(sc, i0, n), rows(se, i0, n), n=n)
+            obj.writeback()
+        # ln-prior zero on the subset, so ln-prob = ln-like; lmap / levid: max and logsumexp of the rows, which fz_sparsify_logwt
+        # forms of the FULL row it is given (here: the row of W entries, one of them kept)
+        lmap, levid = np.zeros(Ndata), np.zeros(Ndata)
+        if resident:
+            if Ndata:
+                eng.dev_copy(lpb, lnl, lnl.nbytes)
+        else:
+            lpb = lnl.copy()
+            lpr = np.where(np.arange(W)[None, :] < cnt[:, None], 0.0, -np.inf)
+            if track_scale and not free:                          # (a fixed scale: 1 and 0 throughout, as ``fit`` leaves them)
+                sc, se = np.ones((Ndata, W)), np.zeros((Ndata, W))
+        if Ndata:
+            eng.sparsify_logwt(lpb, 1, -np.inf, eng.device_empty((Ndata, 1), np.int64), eng.device_empty((Ndata,), np.int64), lmap=lmap,
+                               levid=levid, n=Ndata, M=W)
+        if verbose:
+            sys.stderr.write('\rFitting object {0}/{0}\n'.format(Ndata)); sys.stderr.flush()
+        return SparseFits(nbr, cnt, M, lmap, levid, levid.copy(), lpr, lnl, lpb, ndim, chi2, sc, se, device=self._device)
 
     # -- networks.py:938-1128 ----------------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None, kde_args=None, kde_kwargs=None,

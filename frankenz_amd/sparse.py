@@ -34,7 +34,8 @@ def check_keep(Nkeep, wt_thresh, Nmodel=None):
 
 
 class SparseFits(RowConsumers):
-    """Sparse rows of an exhaustive fit.  ``neighbors`` (Ndata, Nkeep) int64 model indices, best first, padded with -99;
+    """Sparse rows of an exhaustive fit.  ``neighbors`` (Ndata, Nkeep) int64 model indices, best first, padded with -99 (after
+    ``Network.fit_sparse``: in ascending model order; no consumer of the rows looks at their order);
     ``Nneighbors`` (Ndata); the ``fit_*`` arrays (Ndata, Nkeep) padded as ``NearestNeighbors`` pads them (one that was not asked for
     is None); ``lmap`` / ``levid`` of the FULL rows; ``lnkept`` the logsumexp of the kept ln-posteriors; ``NMODEL``."""
 

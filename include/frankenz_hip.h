@@ -346,6 +346,20 @@ int  fz_net_select(fz_ctx* ctx, const double* lnprob, int64_t N, int32_t Nn, int
  * at W; a row of no entry at all (nsel 0, or only empty lists) is W times index 0: the caller must not fit it. */
 int  fz_net_table(fz_ctx* ctx, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, const int32_t* match,
                   const int64_t* csr_off, const int64_t* csr_items, int64_t Nnodes, int64_t W, int64_t* idx);
+/* The union of the selected nodes' lists with repeats removed (extension: Network.fit_sparse; docs/network.md, "Sparse rows").
+ * U_i = the set of model indices in the lists of object i's selected nodes: the node is nd = match ? match[sel[i][s]] : sel[i][s] for
+ * s < nsel[i], its list csr_items[csr_off[nd] .. csr_off[nd + 1]).  nuniq[i] = |U_i|, the full count in either form of the call.
+ * idx != NULL: row i of idx (N, W) holds the elements of U_i in ascending order, cut at W, padded to W with its own first (smallest)
+ * element -- the table fz_knn_fit_predict takes: its first-appearance de-duplication then leaves the ascending order.  An empty union
+ * gives nuniq 0 and W times index 0, as fz_net_table does: the caller must not fit such a row.  idx == NULL is the counting call
+ * (W is not looked at).  An index outside [0, M) in a list that a selected node reaches returns -3; it is found before any row of
+ * idx is written (a bad index in a list no object selects is not an error).  M > FZ_NET_UNION_MMAX = 2^20 is refused with -5: a wave
+ * per object keeps a bitmap of M bits in LDS, four objects per block up to 327 680 models, two up to 655 360, one beyond.  Every
+ * array may live in host or device memory. */
+#define FZ_NET_UNION_MMAX (1 << 20)
+int  fz_net_union(fz_ctx* ctx, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, const int32_t* match,
+                  const int64_t* csr_off, const int64_t* csr_items, int64_t Nnodes, int64_t M, int64_t W, int64_t* nuniq,
+                  int64_t* idx);
 /* networks.py:907-909 (nodes_only): out (N, W) 8-byte elements = plane (N, Nn) at the selected columns, `pad_bits` beyond nsel. */
 int  fz_net_gather(fz_ctx* ctx, const void* plane, const int32_t* nsel, const int32_t* sel, int64_t N, int32_t Nn, int32_t W,
                    uint64_t pad_bits, void* out);
