@@ -720,7 +720,8 @@ class Engine(object):
 
 class DeviceArray(object):
     """A C-contiguous array in an engine's device memory (fz_dev_alloc), with the few tensor-like members the host layer looks at
-    (``shape``, ``data_ptr()``, ``len()``); ``numpy()`` copies it to the host, ``set_rows(r0, a)`` copies ``a`` in at row ``r0``."""
+    (``shape``, ``data_ptr()``, ``len()``); ``numpy()`` copies it to the host, ``set_rows(r0, a)`` copies ``a`` in at row ``r0``,
+    ``row_ptr(r0)`` is the address of that row."""
 
     def __init__(self, eng, shape, dtype=np.float64):
         self.shape = tuple(int(v) for v in np.atleast_1d(shape))
@@ -751,12 +752,17 @@ class DeviceArray(object):
         check(self._eng.lib.fz_dev_copy(self._eng.h, ptr(out), self._ptr, self.nbytes))
         return out
 
+    def row_ptr(self, r0):
+        """the device address of row ``r0`` (one past the last row included: the end of the array)"""
+        if not 0 <= r0 <= self.shape[0]:
+            raise IndexError("row %d of an array of shape %r" % (r0, self.shape))
+        return self._ptr + r0 * self.dtype.itemsize * int(np.prod(self.shape[1:], dtype=np.int64))
+
     def set_rows(self, r0, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)
-        row = self.dtype.itemsize * int(np.prod(self.shape[1:], dtype=np.int64))
         if a.shape[1:] != self.shape[1:] or r0 < 0 or r0 + len(a) > self.shape[0]:
             raise ValueError("rows [%d, %d) do not fit an array of shape %r" % (r0, r0 + len(a), self.shape))
-        check(self._eng.lib.fz_dev_copy(self._eng.h, self._ptr + r0 * row, ptr(a), a.nbytes))
+        check(self._eng.lib.fz_dev_copy(self._eng.h, self.row_ptr(r0), ptr(a), a.nbytes))
 
     def __del__(self):
         try:

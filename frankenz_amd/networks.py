@@ -17,9 +17,10 @@ through the library:
   with repeats removed on the device (``fz_net_union``), sized by the largest union instead of the summed list lengths.
 
 A foreign ``lpnet_func`` / ``lprob_func`` is the user's code: it is called on the host per object exactly as the reference calls it;
-the selection, the unions and the PDFs still run on the device.
+the selection, the unions and the PDFs still run on the device.  The stages these share are listed in docs/network.md, "Python surface".
 """
 import sys
+from collections import namedtuple
 
 import numpy as np
 
@@ -48,24 +49,45 @@ def populate_network(nodes, models, models_err, models_mask, lpnet_kwargs=None, 
     leaves them on the network, plus ``results``: the per-model tuples the generator yields."""
     if lpnet_kwargs is None:
         lpnet_kwargs = {'free_scale': True, 'ignore_model_err': True, 'return_scale': True}
-    if wt_thresh is None and cdf_thresh is None:
-        wt_thresh = -np.inf
     nodes = np.ascontiguousarray(nodes, dtype=np.float64)
     Nnodes, Nmodels = len(nodes), len(models)
     eng = get_engine(device)
-    eng.upload_models(nodes, np.zeros_like(nodes), np.ones_like(nodes))     # networks.py:305-307
-    obj = HostObjects(models, models_err, models_mask)
-    opts = like_opts(lpnet_kwargs)
-    free = bool(opts.free_scale)
     lnprob = np.empty((Nmodels, Nnodes))
     scale = np.ones((Nmodels, Nnodes)); scale_err = np.zeros((Nmodels, Nnodes))
-    want_scale = track_scale and free
-    eng.fit(obj.x, obj.xe, obj.xm, opts, lnprob, None, None, scale if want_scale else None,
-            scale_err if want_scale else None)
-    obj.writeback()
+    free = _fit_nodes(eng, nodes, HostObjects(models, models_err, models_mask), lpnet_kwargs, lnprob,
+                      scale=scale if track_scale else None, scale_err=scale_err if track_scale else None)
     if track_scale and not free:
         raise ValueError("track_scale=True needs a likelihood that returns the scale (free_scale=True)")
     return _lists_from_plane(lnprob, scale, scale_err, wt_thresh, cdf_thresh, track_scale, eng)
+
+
+def _selection_rule(wt_thresh, cdf_thresh):
+    """-> (use_wt, wt_thresh, cdf_thresh) as fz_net_select / fz_som_train take them; neither given: the weight rule at -inf, keep all"""
+    if wt_thresh is None and cdf_thresh is None:
+        wt_thresh = -np.inf
+    use_wt = wt_thresh is not None
+    return use_wt, wt_thresh if use_wt else 0.0, 0.5 if use_wt else cdf_thresh
+
+
+def _fit_nodes(eng, y, obj, lpnet_kwargs, lnprob, chi2=None, ndim=None, scale=None, scale_err=None, n=None):
+    """The built-in node likelihood (networks.py:305-312, 880-882): the nodes ``y`` as noiseless, unmasked models, ``obj`` (HostObjects)
+    fitted into host planes or a device plane (``n``), cleaned and written back.  Returns whether the scale is free (else not filled)."""
+    eng.upload_models(y, np.zeros_like(y), np.ones_like(y))
+    opts = like_opts(lpnet_kwargs)
+    free = bool(opts.free_scale)
+    eng.fit(obj.x, obj.xe, obj.xm, opts, lnprob, chi2, ndim, scale if free else None, scale_err if free else None, n=n)
+    obj.writeback()
+    return free
+
+
+def _foreign_node_rows(lpnet_func, lpnet_args, lpnet_kwargs, y, data, data_err, data_mask, take=None):
+    """the user's ``lpnet_func`` per object as networks.py:310-312, 880-882 call it; its result tuples (or the positions ``take`` of
+    them: nothing else is held) stacked, one array per position"""
+    ye = np.zeros_like(y)
+    ym = np.ones_like(y, dtype='bool')                                     # (a boolean mask, as the reference hands over)
+    calls = (lpnet_func(x, xe, xm, y, ye, ym, *lpnet_args, **lpnet_kwargs) for x, xe, xm in zip(data, data_err, data_mask))
+    rows = [r if take is None else [r[k] for k in take] for r in calls]
+    return [np.ascontiguousarray(np.array([r[k] for r in rows])) for k in range(len(rows[0]))]
 
 
 def _select(eng, lnprob, wt_thresh, cdf_thresh, match=None, csr_off=None, want_stats=False):
@@ -74,10 +96,23 @@ def _select(eng, lnprob, wt_thresh, cdf_thresh, match=None, csr_off=None, want_s
     nsel = np.zeros(n, dtype=np.int32); sel = np.zeros((n, nn), dtype=np.int32)
     rawlen = np.zeros(n, dtype=np.int64) if csr_off is not None else None
     lmap = np.zeros(n) if want_stats else None; levid = np.zeros(n) if want_stats else None
-    use_wt = wt_thresh is not None
-    eng.net_select(lnprob, use_wt, wt_thresh if use_wt else 0.0, 0.5 if use_wt or cdf_thresh is None else cdf_thresh, match, csr_off,
-                   nsel, sel, rawlen, lmap, levid)
+    eng.net_select(lnprob, *_selection_rule(wt_thresh, cdf_thresh), match, csr_off, nsel, sel, rawlen, lmap, levid)
     return nsel, sel, rawlen, lmap, levid
+
+
+def _refuse_no_node(nsel, i0, wt_thresh, cdf_thresh):
+    """(the reference fails here too, in np.max of nothing; a padded table would quietly fit model 0: docs/deviations.md)"""
+    if not nsel.all():
+        use_wt, wt, _ = _selection_rule(wt_thresh, cdf_thresh)
+        raise ValueError("object %d selects no node of the network (%d of %d objects in this call do): its node ln-probabilities "
+                         "hold a nan, or none passes the threshold (wt_thresh=%r, cdf_thresh=%r)"
+                         % (i0 + int(np.argmin(nsel != 0)), int((nsel == 0).sum()), len(nsel), wt if use_wt else None, cdf_thresh))
+
+
+def _refuse_no_model(counts, i0):
+    """(``discrete``: a matched node need not be any model's best one; the reference fails in np.max of nothing)"""
+    if not counts.all():
+        raise ValueError("object %d: the nodes it selects list no model" % (i0 + int(np.argmin(counts != 0))))
 
 
 def _lists_from_plane(lnprob, scale, scale_err, wt_thresh, cdf_thresh, track_scale, eng=None):
@@ -125,15 +160,43 @@ def _lists_from_selection(lnprob, scale, scale_err, nsel, sel, lmap, levid, trac
 
 def _csr(lists):
     """ragged per-node lists -> (offsets int64[Nnodes + 1], items int64)"""
-    lens = np.array([len(v) for v in lists], dtype=np.int64)
     off = np.zeros(len(lists) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
+    np.cumsum([len(v) for v in lists], out=off[1:])
     items = np.concatenate([np.asarray(v, dtype=np.int64) for v in lists]) if off[-1] else np.zeros(1, dtype=np.int64)
     return off, np.ascontiguousarray(items)
 
 
+def _padded(lists, lens, N, W, fill, dtype):
+    """ragged per-row lists (or one scalar per row) -> the (N, W) table: row i holds its ``lens[i]`` entries, then ``fill``"""
+    out = np.full((N, W), fill, dtype=dtype)
+    for i in range(N):
+        out[i, :lens[i]] = lists[i]
+    return out
+
+
 def _is_default(func):
     return func is None or func is _pdf.logprob
+
+
+# the matched nodes: their indices (int64; int32 as the kernels take them), positions and number; the lists of ALL nodes as CSR
+_Matched = namedtuple('_Matched', 'sel sel32 y Nn off items')
+
+
+def _sparse_chunks(eng, mt, lpnet_kwargs, data, thresh, kept, nc, form):
+    """A pass of ``fit_sparse`` over the objects, ``nc`` per device call: yields (i0, n, the staged objects, the device addresses of
+    their nsel / sel) -- rows of ``kept``, the selection of the whole call, or arrays of the chunk's own.  ``form``: the node
+    likelihoods (cleaned in place, written back) and the selection are formed now."""
+    for i0 in range(0, len(data[0]), nc):
+        n = min(nc, len(data[0]) - i0)
+        own = kept or (eng.device_empty((n,), np.int32), eng.device_empty((n, mt.Nn), np.int32))
+        d_nsel, d_sel = [a.row_ptr(i0 if kept else 0) for a in own]
+        obj = HostObjects(*[a[i0:i0 + n] for a in data])
+        if form:
+            plane = eng.device_empty((n, mt.Nn), np.float64)
+            _fit_nodes(eng, mt.y, obj, lpnet_kwargs, plane, n=n)
+            eng.net_select(plane, *_selection_rule(*thresh), None, None, d_nsel, d_sel)
+            del plane                                                  # (a chunk is sized with the plane gone before the tables come)
+        yield i0, n, obj, d_nsel, d_sel
 
 
 class Network(object):
@@ -185,33 +248,23 @@ class Network(object):
                           track_scale=True):
         if self.nodes is None:
             raise ValueError("Network has not been trained!")
-        if lpnet_func is None:
-            lpnet_func = _pdf.logprob
-        if lpnet_args is None:
-            lpnet_args = []
-        if lpnet_kwargs is None:
-            lpnet_kwargs = {'free_scale': True, 'ignore_model_err': True, 'return_scale': True}
-        if wt_thresh is None and cdf_thresh is None:
-            wt_thresh = -np.inf
+        lpnet_func, lpnet_args = _given(lpnet_func, _pdf.logprob), _given(lpnet_args, [])
+        lpnet_kwargs = _given(lpnet_kwargs, {'free_scale': True, 'ignore_model_err': True, 'return_scale': True})
         self.lpnet_func, self.lpnet_args, self.lpnet_kwargs = lpnet_func, lpnet_args, lpnet_kwargs
         if _is_default(lpnet_func) and not lpnet_args:
             m = populate_network(self.nodes, self.models, self.models_err, self.models_mask, lpnet_kwargs=lpnet_kwargs, wt_thresh=wt_thresh,
                                  cdf_thresh=cdf_thresh, track_scale=track_scale, device=self._device)
         else:
-            # the user's node likelihood: called per model as networks.py:310-312 does; selection and lists as above
-            y, ye, ym = self.nodes, np.zeros_like(self.nodes), np.ones_like(self.nodes, dtype='bool')
-            lnprob = np.empty((self.NMODEL, self.NNODE)); sc = np.ones_like(lnprob); se = np.zeros_like(lnprob)
-            for i, (x, xe, xm) in enumerate(zip(self.models, self.models_err, self.models_mask)):
-                r = lpnet_func(x, xe, xm, y, ye, ym, *lpnet_args, **lpnet_kwargs)
-                lnprob[i] = r[2]
-                if track_scale:
-                    sc[i], se[i] = r[5], r[6]
-            m = _lists_from_plane(lnprob, sc, se, wt_thresh, cdf_thresh, track_scale, self._eng())
+            # the user's node likelihood, per model; selection and lists as above
+            planes = _foreign_node_rows(lpnet_func, lpnet_args, lpnet_kwargs, self.nodes, self.models, self.models_err, self.models_mask,
+                                        take=(2, 5, 6) if track_scale else (2,))
+            planes = [np.ascontiguousarray(p, dtype=np.float64) for p in planes]
+            sc, se = planes[1:] if track_scale else (None, None)
+            m = _lists_from_plane(planes[0], sc, se, wt_thresh, cdf_thresh, track_scale, self._eng())
         self.nodes_idxs, self.nodes_logwts, self.nodes_bmus = m.nodes_idxs, m.nodes_logwts, m.nodes_bmus
         self.nodes_scales, self.nodes_scales_err, self.nodes_Nmatch = m.nodes_scales, m.nodes_scales_err, m.nodes_Nmatch
         self.models_lmap, self.models_levid = m.models_lmap, m.models_levid
-        for r in m.results:
-            yield r
+        yield from m.results
 
     # -- networks.py:358-411 -----------------------------------------------------------------------------
     def get_node(self, idx=None, pos=None, discrete=False):
@@ -249,10 +302,8 @@ class Network(object):
         lists = self.nodes_bmus if discrete else self.nodes_idxs
         lens = np.array([len(v) for v in lists], dtype=np.int64)
         W = max(int(lens.max()), 1)
-        nbr = np.zeros((self.NNODE, W), dtype=np.int64); lwt = np.full((self.NNODE, W), -np.inf)
-        for i, v in enumerate(lists):
-            nbr[i, :len(v)] = v
-            lwt[i, :len(v)] = 0.0 if discrete else self.nodes_logwts[i]
+        nbr = _padded(lists, lens, self.NNODE, W, 0, np.int64)
+        lwt = _padded(np.zeros(self.NNODE) if discrete else self.nodes_logwts, lens, self.NNODE, W, -np.inf, np.float64)
         pdfs = np.zeros((self.NNODE, G)); lmap = np.zeros(self.NNODE); levid = np.zeros(self.NNODE)
         eng.knn_predict_logwt(lwt, nbr, lens, W, ko, pdfs, lmap, levid)
         empty = lens == 0
@@ -282,15 +333,10 @@ class Network(object):
         (idxs, Nidx, results[, pdf, (lmap, levid)]) tuples; stores the fits like the reference when save_fits."""
         if self.nodes_idxs is None:
             raise ValueError("Network has not been trained!")
-        lprob_args = lprob_args or []
-        lprob_kwargs = lprob_kwargs or {}
-        if wt_thresh is None and cdf_thresh is None:
-            wt_thresh = -np.inf
+        lprob = (lprob_func, lprob_args or [], lprob_kwargs or {})
         eng = self._eng()
         Ndata = len(data)
-        match_sel = np.arange(self.NNODE)[self.nodes_Nmatch > 0]
-        match32 = np.ascontiguousarray(match_sel, dtype=np.int32)
-        y = np.ascontiguousarray(self.nodes[match_sel]); Nn = len(y)
+        mt = self._matched(discrete)
         self.nodes_only = nodes_only
         if save_fits:
             self.NDATA = Ndata
@@ -298,123 +344,119 @@ class Network(object):
             self.fit_lnprior, self.fit_lnlike, self.fit_lnprob, self.fit_Ndim, self.fit_chi2 = [], [], [], [], []
             self.fit_scale, self.fit_scale_err = [], []
         node_pdfs = None
-        ko = G = None
-        if predict is not None:
-            labels, label_errs, label_dict, label_grid, kde_args, kde_kwargs = predict
-            if nodes_only:
-                node_pdfs = np.ascontiguousarray(self.get_pdfs(labels, label_errs, label_dict, label_grid, kde_args, kde_kwargs,
-                                                               False, discrete, False))
-                G = node_pdfs.shape[1]
-        off, items = _csr(self.nodes_bmus if discrete else self.nodes_idxs)
-        lp_default = _is_default(self.lpnet_func) and not self.lpnet_args
-        host_lprob = not (_is_default(lprob_func) and not lprob_args)
+        if predict is not None and nodes_only:
+            node_pdfs = np.ascontiguousarray(self.get_pdfs(*predict, False, discrete, False))
         out = []
         for i0 in range(0, Ndata, _NET_CHUNK):
-            sl = slice(i0, min(i0 + _NET_CHUNK, Ndata)); n = sl.stop - sl.start
-            obj = HostObjects(data[sl], data_err[sl], data_mask[sl])
-            # node likelihoods (networks.py:880-882): the matched nodes as noiseless, unmasked models
-            lnp = np.empty((n, Nn)); chi2 = np.empty((n, Nn)); ndim = np.empty((n, Nn), dtype=np.int64)
-            sc = np.ones((n, Nn)); se = np.zeros((n, Nn))
-            if lp_default:
-                eng.upload_models(y, np.zeros_like(y), np.ones_like(y))
-                nopts = like_opts(self.lpnet_kwargs)
-                free = bool(nopts.free_scale)
-                eng.fit(obj.x, obj.xe, obj.xm, nopts, lnp, chi2, ndim, sc if free else None, se if free else None)
-                obj.writeback()
-                nres = [np.zeros((n, Nn)), lnp, lnp, ndim, chi2, sc, se]
-            else:
-                ye, ym = np.zeros_like(y), np.ones_like(y, dtype='bool')
-                rows = [self.lpnet_func(x, xe, xm, y, ye, ym, *self.lpnet_args, **self.lpnet_kwargs)
-                        for x, xe, xm in zip(data[sl], data_err[sl], data_mask[sl])]
-                nres = [np.ascontiguousarray(np.array([r[k] for r in rows])) for k in range(len(rows[0]))]
-                lnp = np.ascontiguousarray(nres[2], dtype=np.float64)
-            nsel, sel, rawlen, _, _ = _select(eng, lnp, wt_thresh, cdf_thresh, match32, None if nodes_only else off)
-            if not nsel.all():
-                # (the reference fails here too, in np.max of nothing; a padded table would quietly fit model 0: docs/deviations.md)
-                k = int(np.argmin(nsel != 0))
-                raise ValueError("object %d selects no node of the network (%d of %d objects in this call do): its node ln-probabilities "
-                                 "hold a nan, or none passes the threshold (wt_thresh=%r, cdf_thresh=%r)"
-                                 % (i0 + k, int((nsel == 0).sum()), n, wt_thresh, cdf_thresh))
+            sl = slice(i0, min(i0 + _NET_CHUNK, Ndata))
+            chunk = (data[sl], data_err[sl], data_mask[sl])
+            obj = HostObjects(*chunk)
+            nres, lnp, width = self._node_results(eng, mt, obj, chunk)
+            nsel, sel, rawlen, _, _ = _select(eng, lnp, wt_thresh, cdf_thresh, mt.sel32, None if nodes_only else mt.off)
+            _refuse_no_node(nsel, i0, wt_thresh, cdf_thresh)
             if nodes_only:
-                W = max(int(nsel.max()), 1)
-                res = []
-                for k, pl in enumerate(nres):
-                    pl = np.ascontiguousarray(pl)
-                    if pl.dtype not in (np.float64, np.int64):
-                        pl = pl.astype(np.float64)
-                    g = np.empty((n, W), dtype=pl.dtype)
-                    eng.net_gather(pl, nsel, sel, W, 0, g)
-                    res.append(g)
-                nb = np.empty((n, W), dtype=np.int64)
-                eng.net_gather(np.ascontiguousarray(np.broadcast_to(match_sel.astype(np.int64), (n, Nn))), nsel, sel, W, -99, nb)
-                nn_ = nsel.astype(np.int64)
-                pdfs = lmap = levid = None
-                if predict is not None:
-                    pdfs = np.empty((n, G)); lmap = np.empty(n); levid = np.empty(n)
-                    eng.net_stack(lnp, nsel, sel, match32, node_pdfs, pdfs, lmap, levid)
+                fit = self._fit_nodes_only(eng, mt, nres, lnp, width, nsel, sel, node_pdfs)
             else:
-                W = max(int(rawlen.max()), 1)
-                if not rawlen.all():
-                    # (`discrete`: a matched node need not be any model's best one; the reference fails in np.max of nothing)
-                    raise ValueError("object %d: the nodes it selects list no model" % (i0 + int(np.argmin(rawlen != 0))))
-                if W > _UNION_MAX:
-                    raise NotImplementedError("object %d: its selected nodes list %d models before repeats are removed; the union table "
-                                              "of fz_knn_fit_predict holds at most %d (this is not the limit of %d matched nodes)"
-                                              % (i0 + int(np.argmax(rawlen)), W, _UNION_MAX, _NODES_MAX))
-                idx = np.empty((n, W), dtype=np.int64)
-                eng.net_table(nsel, sel, match32, off, items, W, idx)
-                nb = np.empty((n, W), dtype=np.int64); nn_ = np.empty(n, dtype=np.int64)
-                eng.upload_models(self.models, self.models_err, self.models_mask)
-                pdfs = lmap = levid = None
-                if predict is not None:
-                    ko, G = self._labels(eng, labels, label_errs, label_dict, label_grid, kde_args, kde_kwargs)
-                    pdfs = np.empty((n, G)); lmap = np.empty(n); levid = np.empty(n)
-                opts = like_opts({} if host_lprob else lprob_kwargs)
-                lnl = np.empty((n, W)); c2 = np.empty((n, W)); nd = np.empty((n, W), dtype=np.int64)
-                s_ = np.empty((n, W)); se_ = np.empty((n, W))
-                eng.knn_fit_predict(obj.x, obj.xe, obj.xm, idx, W, opts, ko, nb, nn_, lnl, c2, nd, s_, se_,
-                                    None if host_lprob else pdfs, None if host_lprob else lmap, None if host_lprob else levid)
-                obj.writeback()
-                if host_lprob:
-                    # the user's likelihood on each object's model subset (networks.py:925-928), the PDFs from its ln-posteriors
-                    lw = np.full((n, W), -np.inf)
-                    rows = []
-                    for k in range(n):
-                        ii = nb[k, :nn_[k]]
-                        r = lprob_func(data[sl][k], data_err[sl][k], data_mask[sl][k], self.models[ii], self.models_err[ii],
-                                       self.models_mask[ii], *lprob_args, **lprob_kwargs)
-                        rows.append(r); lw[k, :nn_[k]] = r[2]
-                    if predict is not None:
-                        # (the user's function may have used this device's context itself -- the package's own logprob does: the model and
-                        #  label sets are put back before the PDFs are stacked)
-                        ko, G = self._labels(eng, labels, label_errs, label_dict, label_grid, kde_args, kde_kwargs)
-                        eng.knn_predict_logwt(lw, nb, nn_, W, ko, pdfs, lmap, levid)
-                    res = rows
-                else:
-                    res = [np.zeros((n, W)), lnl, lnl, nd, c2, s_, se_]
-            for k in range(n):
-                m = int(nn_[k])
-                idxs = nb[k, :m].copy()
-                if isinstance(res, list) and len(res) and isinstance(res[0], tuple):
-                    results = res[k]
-                else:
-                    results = [r[k, :m].copy() for r in res]
-                    # (pdf.logprob returns seven arrays with return_scale, else five: pdf.py:404-411)
-                    seven = (len(nres) > 5 and (not lp_default or self.lpnet_kwargs.get('return_scale', False))) if nodes_only \
-                        else bool(lprob_kwargs.get('return_scale', False))
-                    if not seven:
-                        results = results[:5]
-                if save_fits:
-                    self.Nneighbors[i0 + k] = m
-                    self.neighbors.append(np.array(idxs))
-                    self.fit_lnprior.append(results[0]); self.fit_lnlike.append(results[1]); self.fit_lnprob.append(results[2])
-                    self.fit_Ndim.append(results[3]); self.fit_chi2.append(results[4])
-                    if track_scale:
-                        self.fit_scale.append(results[5]); self.fit_scale_err.append(results[6])
-                if predict is not None:
-                    out.append((idxs, m, results, pdfs[k], (lmap[k], levid[k])))
-                else:
-                    out.append((idxs, m, results))
+                _refuse_no_model(rawlen, i0)
+                fit = self._fit_union(eng, mt, obj, chunk, i0, nsel, sel, rawlen, lprob, predict)
+            out += self._emit(i0, save_fits, track_scale, *fit)
+        return out
+
+    def _matched(self, discrete):
+        sel = np.arange(self.NNODE)[self.nodes_Nmatch > 0]
+        y = np.ascontiguousarray(self.nodes[sel])
+        return _Matched(sel, np.ascontiguousarray(sel, dtype=np.int32), y, len(y), *_csr(self.nodes_bmus if discrete else self.nodes_idxs))
+
+    def _node_results(self, eng, mt, obj, chunk):
+        """Node likelihoods of one chunk (networks.py:880-882): the (n, Nn) planes of the result tuple, the ln-probabilities as the
+        selection takes them, how many planes ``nodes_only`` hands out (pdf.logprob: seven with return_scale, else five; the user's: all)"""
+        if not (_is_default(self.lpnet_func) and not self.lpnet_args):
+            nres = _foreign_node_rows(self.lpnet_func, self.lpnet_args, self.lpnet_kwargs, mt.y, *chunk)
+            return nres, np.ascontiguousarray(nres[2], dtype=np.float64), len(nres)
+        n, Nn = len(obj.x), mt.Nn
+        lnp = np.empty((n, Nn)); chi2 = np.empty((n, Nn)); ndim = np.empty((n, Nn), dtype=np.int64)
+        sc = np.ones((n, Nn)); se = np.zeros((n, Nn))
+        _fit_nodes(eng, mt.y, obj, self.lpnet_kwargs, lnp, chi2, ndim, sc, se)
+        return [np.zeros((n, Nn)), lnp, lnp, ndim, chi2, sc, se], lnp, 7 if self.lpnet_kwargs.get('return_scale', False) else 5
+
+    def _fit_nodes_only(self, eng, mt, nres, lnp, width, nsel, sel, node_pdfs):
+        """the selected nodes as the models (networks.py:907-909, 1463-1470): their results gathered, their PDFs stacked by weight"""
+        n, W = len(nsel), max(int(nsel.max()), 1)
+        res = []
+        for pl in nres:
+            pl = np.ascontiguousarray(pl)
+            if pl.dtype not in (np.float64, np.int64):
+                pl = pl.astype(np.float64)
+            g = np.empty((n, W), dtype=pl.dtype)
+            eng.net_gather(pl, nsel, sel, W, 0, g)
+            res.append(g)
+        nb = np.empty((n, W), dtype=np.int64)
+        eng.net_gather(np.ascontiguousarray(np.broadcast_to(mt.sel.astype(np.int64), (n, mt.Nn))), nsel, sel, W, -99, nb)
+        pdfs = lmap = levid = None
+        if node_pdfs is not None:
+            pdfs = np.empty((n, node_pdfs.shape[1])); lmap = np.empty(n); levid = np.empty(n)
+            eng.net_stack(lnp, nsel, sel, mt.sel32, node_pdfs, pdfs, lmap, levid)
+        return nb, nsel.astype(np.int64), lambda k, m: [p[k, :m].copy() for p in res[:width]], pdfs, lmap, levid
+
+    def _fit_union(self, eng, mt, obj, chunk, i0, nsel, sel, rawlen, lprob, predict):
+        """the union of the selected nodes' lists as the models (networks.py:913-936, 1413-1460); ``lprob`` = (func, args, kwargs)"""
+        lprob_func, lprob_args, lprob_kwargs = lprob
+        host_lprob = not (_is_default(lprob_func) and not lprob_args)
+        n, W = len(nsel), max(int(rawlen.max()), 1)
+        if W > _UNION_MAX:
+            raise NotImplementedError("object %d: its selected nodes list %d models before repeats are removed; the union table "
+                                      "of fz_knn_fit_predict holds at most %d (this is not the limit of %d matched nodes)"
+                                      % (i0 + int(np.argmax(rawlen)), W, _UNION_MAX, _NODES_MAX))
+        idx = np.empty((n, W), dtype=np.int64)
+        eng.net_table(nsel, sel, mt.sel32, mt.off, mt.items, W, idx)
+        nb = np.empty((n, W), dtype=np.int64); nn_ = np.empty(n, dtype=np.int64)
+        eng.upload_models(self.models, self.models_err, self.models_mask)
+        ko = pdfs = lmap = levid = None
+        if predict is not None:
+            ko, G = self._labels(eng, *predict)
+            pdfs = np.empty((n, G)); lmap = np.empty(n); levid = np.empty(n)
+        opts = like_opts({} if host_lprob else lprob_kwargs)
+        lnl = np.empty((n, W)); c2 = np.empty((n, W)); nd = np.empty((n, W), dtype=np.int64)
+        s_ = np.empty((n, W)); se_ = np.empty((n, W))
+        eng.knn_fit_predict(obj.x, obj.xe, obj.xm, idx, W, opts, ko, nb, nn_, lnl, c2, nd, s_, se_,
+                            *((None, None, None) if host_lprob else (pdfs, lmap, levid)))
+        obj.writeback()
+        if not host_lprob:
+            planes = [np.zeros((n, W)), lnl, lnl, nd, c2, s_, se_][:7 if lprob_kwargs.get('return_scale', False) else 5]
+            return nb, nn_, lambda k, m: [p[k, :m].copy() for p in planes], pdfs, lmap, levid
+        # the user's likelihood on each object's model subset (networks.py:925-928), the PDFs from its ln-posteriors; the result of
+        # an object is the user's own tuple, as it came
+        X, Xe, Xm = chunk
+        lw = np.full((n, W), -np.inf)
+        rows = []
+        for k in range(n):
+            ii = nb[k, :nn_[k]]
+            r = lprob_func(X[k], Xe[k], Xm[k], self.models[ii], self.models_err[ii], self.models_mask[ii], *lprob_args, **lprob_kwargs)
+            rows.append(r); lw[k, :nn_[k]] = r[2]
+        if predict is not None:
+            # (the user's function may have used this device's context itself -- the package's own logprob does: the model and
+            #  label sets are put back before the PDFs are stacked)
+            ko, _ = self._labels(eng, *predict)
+            eng.knn_predict_logwt(lw, nb, nn_, W, ko, pdfs, lmap, levid)
+        return nb, nn_, lambda k, m: rows[k], pdfs, lmap, levid
+
+    def _emit(self, i0, save_fits, track_scale, nb, nn, results_of, pdfs, lmap, levid):
+        """What a fit path returns of the chunk at ``i0`` -- neighbour table (n, W), counts (n), ``results_of(k, m)`` = the result tuple
+        of object k with its m neighbours, PDFs with lmap / levid or None -- as per-object tuples (idxs, Nidx, results[, pdf, (lmap,
+        levid)]); stores the fits like the reference when save_fits."""
+        out = []
+        for k in range(len(nn)):
+            m = int(nn[k])
+            idxs = nb[k, :m].copy()
+            results = results_of(k, m)
+            if save_fits:
+                self.Nneighbors[i0 + k] = m
+                self.neighbors.append(np.array(idxs))
+                self.fit_lnprior.append(results[0]); self.fit_lnlike.append(results[1]); self.fit_lnprob.append(results[2])
+                self.fit_Ndim.append(results[3]); self.fit_chi2.append(results[4])
+                if track_scale:
+                    self.fit_scale.append(results[5]); self.fit_scale_err.append(results[6])
+            out.append((idxs, m, results) if pdfs is None else (idxs, m, results, pdfs[k], (lmap[k], levid[k])))
         return out
 
     # -- networks.py:782-936 -----------------------------------------------------------------------------
@@ -427,9 +469,8 @@ class Network(object):
 
     def _fit(self, data, data_err, data_mask, lprob_func=None, nodes_only=False, wt_thresh=1e-3, cdf_thresh=2e-4, lprob_args=None,
              lprob_kwargs=None, track_scale=False, discrete=False, save_fits=True):
-        for r in self._run(data, data_err, data_mask, lprob_func, nodes_only, wt_thresh, cdf_thresh, lprob_args, lprob_kwargs,
-                           track_scale, discrete, save_fits):
-            yield r
+        yield from self._run(data, data_err, data_mask, lprob_func, nodes_only, wt_thresh, cdf_thresh, lprob_args, lprob_kwargs,
+                             track_scale, discrete, save_fits)
 
     # -- extension: the fit as sparse rows (docs/network.md, "Sparse rows") ---------------------------------------------------
     def fit_sparse(self, data, data_err, data_mask, lprob_func=None, wt_thresh=1e-3, cdf_thresh=2e-4, lprob_args=None,
@@ -445,7 +486,6 @@ class Network(object):
         attribute of this object is touched; the in-place clean of the objects reaches the caller's arrays.  ``resident=True``
         leaves ``neighbors``, ``Nneighbors``, ``fit_lnlike`` and ``fit_lnprob`` as device arrays of the engine (the other ``fit_*``
         are then None)."""
-        from .sparse import SparseFits
         if self.nodes_idxs is None:
             raise ValueError("Network has not been trained!")
         if not (_is_default(lprob_func) and not lprob_args):
@@ -457,65 +497,38 @@ class Network(object):
             raise NotImplementedError("%d models exceed FZ_NET_UNION_MMAX = %d (an object's bitmap of the models sits in LDS)"
                                       % (self.NMODEL, _UNION_MMAX))
         opts = like_opts(lprob_kwargs)
-        nopts = like_opts(self.lpnet_kwargs)
-        if wt_thresh is None and cdf_thresh is None:
-            wt_thresh = -np.inf
-        use_wt = wt_thresh is not None
-        sel_args = (use_wt, wt_thresh if use_wt else 0.0, 0.5 if use_wt or cdf_thresh is None else cdf_thresh)
-        eng = self._eng()
-        Ndata, M = len(data), self.NMODEL
-        match_sel = np.arange(self.NNODE)[self.nodes_Nmatch > 0]
-        match32 = np.ascontiguousarray(match_sel, dtype=np.int32)
-        y = np.ascontiguousarray(self.nodes[match_sel]); Nn = len(y)
-        off, items = _csr(self.nodes_bmus if discrete else self.nodes_idxs)
-        d_match, d_off, d_items = eng.device_array(match32), eng.device_array(off), eng.device_array(items)
+        eng, mt, Ndata, thresh = self._eng(), self._matched(discrete), len(data), (wt_thresh, cdf_thresh)
+        lists = eng.device_array(mt.sel32), eng.device_array(mt.off), eng.device_array(mt.items)
         # Objects per device call: the (n, Nn) node plane, sel (n, Nn) int32, nsel and the counts inside a quarter of the workspace
         # budget.  The selection of the counting pass stays on the device for the fitting pass while all of it fits another quarter;
         # otherwise the fitting pass forms it again, chunk by chunk.
         limit = eng.workspace_limit()
-        sel_row = Nn * 4 + 4
+        sel_row = mt.Nn * 4 + 4
         keep = Ndata * sel_row <= limit // 4
-        nc1 = int(max(1, min(_NET_CHUNK, (limit // 4) // (Nn * 8 + (0 if keep else sel_row) + 8))))
-
-        def select(i0, n, d_nsel, d_sel):
-            """the node likelihoods of objects [i0, i0 + n) (cleaned in place, written back) and their selection, on the device"""
-            obj = HostObjects(data[i0:i0 + n], data_err[i0:i0 + n], data_mask[i0:i0 + n])
-            plane = eng.device_empty((n, Nn), np.float64)
-            eng.upload_models(y, np.zeros_like(y), np.ones_like(y))
-            eng.fit(obj.x, obj.xe, obj.xm, nopts, plane, n=n)
-            obj.writeback()
-            eng.net_select(plane, *sel_args, None, None, d_nsel, d_sel)
-            return obj
-
+        kept = (eng.device_empty((Ndata,), np.int32), eng.device_empty((Ndata, mt.Nn), np.int32)) if keep and Ndata else None
+        chunks = lambda per_object, form: _sparse_chunks(eng, mt, self.lpnet_kwargs, (data, data_err, data_mask), thresh, kept,
+                                                         int(max(1, min(_NET_CHUNK, (limit // 4) // per_object))), form)
         # ---- pass 1: the selections and the sizes of the unions; every refusal falls here, before the first subset fit ----
         nuniq = np.zeros(Ndata, dtype=np.int64)
-        if keep and Ndata:
-            all_nsel, all_sel = eng.device_empty((Ndata,), np.int32), eng.device_empty((Ndata, Nn), np.int32)
-        for i0 in range(0, Ndata, nc1):
-            n = min(nc1, Ndata - i0)
-            if keep:
-                d_nsel, d_sel = all_nsel.data_ptr() + i0 * 4, all_sel.data_ptr() + i0 * Nn * 4
-                hold = None
-            else:
-                hold = (eng.device_empty((n,), np.int32), eng.device_empty((n, Nn), np.int32))
-                d_nsel, d_sel = hold[0].data_ptr(), hold[1].data_ptr()
-            select(i0, n, d_nsel, d_sel)
+        for i0, n, _, d_nsel, d_sel in chunks(mt.Nn * 8 + (0 if keep else sel_row) + 8, True):
             nsel = np.empty(n, dtype=np.int32)
             eng.dev_copy(nsel, d_nsel, nsel.nbytes)
-            if not nsel.all():
-                k = int(np.argmin(nsel != 0))
-                raise ValueError("object %d selects no node of the network (%d of %d objects in this call do): its node ln-probabilities "
-                                 "hold a nan, or none passes the threshold (wt_thresh=%r, cdf_thresh=%r)"
-                                 % (i0 + k, int((nsel == 0).sum()), n, wt_thresh, cdf_thresh))
-            eng.net_union(d_nsel, d_sel, d_match, d_off, d_items, M, nuniq[i0:i0 + n], n=n, nn=Nn)
-            if not nuniq[i0:i0 + n].all():
-                raise ValueError("object %d: the nodes it selects list no model" % (i0 + int(np.argmin(nuniq[i0:i0 + n] != 0))))
+            _refuse_no_node(nsel, i0, *thresh)
+            eng.net_union(d_nsel, d_sel, *lists, self.NMODEL, nuniq[i0:i0 + n], n=n, nn=mt.Nn)
+            _refuse_no_model(nuniq[i0:i0 + n], i0)
         W = max(int(nuniq.max()), 1) if Ndata else 1
         if W > _UNION_MAX:
             raise NotImplementedError("object %d: its selected nodes list %d different models; the union table of fz_knn_fit_predict "
                                       "holds at most FZ_KNN_WMAX = %d" % (int(np.argmax(nuniq)), W, _UNION_MAX))
+        sf = self._sparse_rows(eng, mt, lists, chunks(W * 8 + (0 if keep else mt.Nn * 8 + sel_row), not keep), Ndata, W, opts,
+                               track_scale, resident)
+        if verbose:
+            sys.stderr.write('\rFitting object {0}/{0}\n'.format(Ndata)); sys.stderr.flush()
+        return sf
 
-        # ---- pass 2: the tables and the subset likelihood, straight into rows [i0, i0 + n) of the (Ndata, W) outputs ----
+    def _sparse_rows(self, eng, mt, lists, chunks, Ndata, W, opts, track_scale, resident):
+        """pass 2 of ``fit_sparse``: the tables and the subset likelihood, straight into rows [i0, i0 + n) of the (Ndata, W) outputs"""
+        from .sparse import SparseFits
         free = track_scale and bool(opts.free_scale)
         if resident:
             new = lambda dt: eng.device_empty((Ndata, W), dt)
@@ -527,29 +540,15 @@ class Network(object):
             nbr, cnt = new(np.int64), np.zeros(Ndata, dtype=np.int64)
             lnl, chi2, ndim = new(np.float64), new(np.float64), new(np.int64)
             sc, se = (new(np.float64), new(np.float64)) if free else (None, None)
-
-        def rows(a, i0, n, width=W):
-            """rows [i0, i0 + n) of an output: a view of a host array, a raw pointer into a device array"""
-            if a is None:
-                return None
-            return a[i0:i0 + n] if isinstance(a, np.ndarray) else a.data_ptr() + i0 * width * 8
-
-        nc2 = int(max(1, min(_NET_CHUNK, (limit // 4) // (W * 8 + (0 if keep else Nn * 8 + sel_row)))))
-        for i0 in range(0, Ndata, nc2):
-            n = min(nc2, Ndata - i0)
-            if keep:
-                d_nsel, d_sel = all_nsel.data_ptr() + i0 * 4, all_sel.data_ptr() + i0 * Nn * 4
-                obj = HostObjects(data[i0:i0 + n], data_err[i0:i0 + n], data_mask[i0:i0 + n])
-            else:
-                hold = (eng.device_empty((n,), np.int32), eng.device_empty((n, Nn), np.int32))
-                d_nsel, d_sel = hold[0].data_ptr(), hold[1].data_ptr()
-                obj = select(i0, n, d_nsel, d_sel)
+        for i0, n, obj, d_nsel, d_sel in chunks:
             idx = eng.device_empty((n, W), np.int64)
             nu = eng.device_empty((n,), np.int64)
-            eng.net_union(d_nsel, d_sel, d_match, d_off, d_items, M, nu, W, idx, n=n, nn=Nn)
+            eng.net_union(d_nsel, d_sel, *lists, self.NMODEL, nu, W, idx, n=n, nn=mt.Nn)
             eng.upload_models(self.models, self.models_err, self.models_mask)
-            eng.knn_fit_predict(obj.x, obj.xe, obj.xm, idx, W, opts, None, rows(nbr, i0, n), rows(cnt, i0, n, 1), rows(lnl, i0, n),
-                                rows(chi2, i0, n), rows(ndim, i0, n), rows(sc, i0, n), rows(se, i0, n), n=n)
+            # (rows of an output: a view of a host array, the address of the row in a device array)
+            rows = [a if a is None else a[i0:i0 + n] if isinstance(a, np.ndarray) else a.row_ptr(i0)
+                    for a in (nbr, cnt, lnl, chi2, ndim, sc, se)]
+            eng.knn_fit_predict(obj.x, obj.xe, obj.xm, idx, W, opts, None, *rows, n=n)
             obj.writeback()
         # ln-prior zero on the subset, so ln-prob = ln-like; lmap / levid: max and logsumexp of the rows, which fz_sparsify_logwt
         # forms of the FULL row it is given (here: the row of W entries, one of them kept)
@@ -565,9 +564,7 @@ class Network(object):
         if Ndata:
             eng.sparsify_logwt(lpb, 1, -np.inf, eng.device_empty((Ndata, 1), np.int64), eng.device_empty((Ndata,), np.int64), lmap=lmap,
                                levid=levid, n=Ndata, M=W)
-        if verbose:
-            sys.stderr.write('\rFitting object {0}/{0}\n'.format(Ndata)); sys.stderr.flush()
-        return SparseFits(nbr, cnt, M, lmap, levid, levid.copy(), lpr, lnl, lpb, ndim, chi2, sc, se, device=self._device)
+        return SparseFits(nbr, cnt, self.NMODEL, lmap, levid, levid.copy(), lpr, lnl, lpb, ndim, chi2, sc, se, device=self._device)
 
     # -- networks.py:938-1128 ----------------------------------------------------------------------------
     def predict(self, model_labels, model_label_errs, label_dict=None, label_grid=None, logwt=None, kde_args=None, kde_kwargs=None,
@@ -582,10 +579,8 @@ class Network(object):
         N = self.NDATA
         lens = np.array([len(v) for v in logwt], dtype=np.int64)
         W = max(int(lens.max()), 1)
-        lw = np.full((N, W), -np.inf); nb = np.zeros((N, W), dtype=np.int64)
-        for i in range(N):
-            lw[i, :lens[i]] = logwt[i]
-            nb[i, :lens[i]] = self.neighbors[i] if not self.nodes_only else 0
+        lw = _padded(logwt, lens, N, W, -np.inf, np.float64)
+        nb = _padded(np.zeros(N, dtype=np.int64) if self.nodes_only else self.neighbors, lens, N, W, 0, np.int64)
         if self.nodes_only:
             # stack the node PDFs by the relative weights of the stored node fits (networks.py:1113-1115)
             node_pdfs = np.ascontiguousarray(self.get_pdfs(model_labels, model_label_errs, label_dict, label_grid, kde_args, kde_kwargs,
@@ -816,8 +811,7 @@ class SelfOrganizingMap(Network):
         neighbor_func = _given(neighbor_func, neighbor_gauss)
         neighbor_args, neighbor_kwargs = _given(neighbor_args, []), _given(neighbor_kwargs, {})
         rstate = _given(rstate, np.random)
-        if wt_thresh is None and cdf_thresh is None:
-            wt_thresh = -np.inf                                           # no thresholding at all
+        use_wt, wt, cdf = _selection_rule(wt_thresh, cdf_thresh)          # (neither given: no thresholding at all)
         T = niter * nbatch
         times = np.linspace(0., 1., T)
         self.NITER, self.NBATCH = niter, nbatch
@@ -829,7 +823,7 @@ class SelfOrganizingMap(Network):
         if not (_is_default(lprob_func) and not lprob_args and neighbor_func in (neighbor_gauss, neighbor_lorentz)):
             for step in self._som_host_steps(models, models_err, models_mask, times, rstate, lprob_func, lprob_args, lprob_kwargs,
                                              learn_func, learn_args, learn_kwargs, neighbor_func, neighbor_args, neighbor_kwargs,
-                                             wt_thresh, cdf_thresh, track_scale):
+                                             wt if use_wt else None, cdf_thresh, track_scale):
                 yield step
             return
 
@@ -845,13 +839,11 @@ class SelfOrganizingMap(Network):
         bmus = np.zeros(T, dtype=np.int32)
         eng = self._eng()
         kind = 0 if neighbor_func is neighbor_gauss else 1
-        use_wt = wt_thresh is not None
         dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, dbmus = _device_arrays(eng.device, (x, xe, xm, nodes, pos, draws, lr, sig, bmus))
         seg = max(1, int(_SOM_SEGMENT))
         for s0 in range(0, T, seg):
             s1 = min(T, s0 + seg)
-            eng.som_train(dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, kind, use_wt, wt_thresh if use_wt else 0.,
-                          0.5 if use_wt else cdf_thresh, opts, track_scale, s0, s1, dbmus)
+            eng.som_train(dx, dxe, dxm, dnodes, dpos, ddraws, dlr, dsig, kind, use_wt, wt, cdf, opts, track_scale, s0, s1, dbmus)
             if dnodes is not nodes:
                 nodes[...] = dnodes.cpu().numpy()
                 bmus[s0:s1] = dbmus[s0:s1].cpu().numpy()

@@ -173,6 +173,14 @@ def test_width_at_the_limit_and_refusals():
     net = make_net(g)
     with pytest.raises(ValueError, match=r'object 0 selects no node .*\(%d of %d objects' % (len(X), len(X))):
         net.fit_sparse(X.copy(), Xe.copy(), Xm.copy(), wt_thresh=1.0, verbose=False)
+    # ... in the very words of ``fit``: one expression matches both
+    words = (r'^object 0 selects no node of the network \(%d of %d objects in this call do\): its node ln-probabilities hold a nan, or '
+             r'none passes the threshold \(wt_thresh=1\.0, cdf_thresh=0\.0002\)$' % (len(X), len(X)))
+    with pytest.raises(ValueError, match=words) as sparse:
+        net.fit_sparse(X.copy(), Xe.copy(), Xm.copy(), wt_thresh=1.0, verbose=False)
+    with pytest.raises(ValueError, match=words) as dense:
+        net.fit(X.copy(), Xe.copy(), Xm.copy(), wt_thresh=1.0, verbose=False)
+    assert str(sparse.value) == str(dense.value)
     net.nodes_bmus = [[] for _ in range(net.NNODE)]
     with pytest.raises(ValueError, match='object 0: the nodes it selects list no model'):
         net.fit_sparse(X.copy(), Xe.copy(), Xm.copy(), discrete=True, verbose=False)

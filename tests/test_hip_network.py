@@ -129,6 +129,121 @@ def test_user_callables_run_on_the_host_and_match_the_device_path():
     np.testing.assert_array_equal(cat(net.neighbors, 'int'), cat(net2.neighbors, 'int'))
 
 
+# ---- the host layer's own paths: chunk seams, the layout of the yielded tuples, save_fits, a foreign likelihood on a label grid ------
+FIT_LISTS = ('neighbors', 'fit_lnprior', 'fit_lnlike', 'fit_lnprob', 'fit_Ndim', 'fit_chi2', 'fit_scale', 'fit_scale_err')
+
+
+def g14_objects(g):
+    return g['data'].copy(), g['data_err'].copy(), g['data_mask'].copy()
+
+
+def stored_and_pdfs(g, d):
+    """what fit_predict (nodes_only 0 / 1) and fit leave on the network and return, on the G14 objects"""
+    out = {}
+    for call in ('fit_predict_n0', 'fit_predict_n1', 'fit'):
+        net = make_net(g)
+        with np.errstate(all='ignore'):
+            if call == 'fit':
+                net.fit(*g14_objects(g), verbose=False)
+                got = {}
+            else:
+                nodes_only = call.endswith('1')
+                pdfs, (lm, le) = net.fit_predict(*g14_objects(g), g['labels'], g['label_errs'], label_dict=d, nodes_only=nodes_only,
+                                                 track_scale=nodes_only, save_fits=True, return_gof=True, verbose=False)
+                got = dict(pdfs=pdfs, lmap=lm, levid=le)
+        got['Nneighbors'] = net.Nneighbors
+        for k in FIT_LISTS:
+            got[k] = getattr(net, k)
+        out[call] = got
+    return out
+
+
+def test_a_chunk_seam_inside_the_objects_changes_no_bit():
+    """7 objects per device call: a seam inside the 14 objects of G14; 5: two seams and a short last chunk of 4.  The stored fits and
+    the PDFs are those of one chunk, bit for bit"""
+    from frankenz_amd import networks
+    g = load_golden('g14_network_inference')
+    d, _ = dicts()
+    N = len(g['data'])
+    assert N > 7 and N % 5 != 0
+    whole = stored_and_pdfs(g, d)
+    default = networks._NET_CHUNK
+    cuts = []
+    try:
+        for chunk in (7, 5):
+            networks._NET_CHUNK = chunk
+            cuts.append(stored_and_pdfs(g, d))
+    finally:
+        networks._NET_CHUNK = default
+    for cut, (call, want) in [(c, cw) for c in cuts for cw in whole.items()]:
+        got = cut[call]
+        assert got.keys() == want.keys()
+        for k in want:
+            if k in FIT_LISTS:
+                assert len(got[k]) == len(want[k]) and len(want[k]) in (0, N), (call, k)
+                for a, b in zip(got[k], want[k]):
+                    np.testing.assert_array_equal(a, b, err_msg='%s %s' % (call, k))
+            else:
+                np.testing.assert_array_equal(got[k], want[k], err_msg='%s %s' % (call, k))
+        assert len(want['fit_lnprob']) == N and (call != 'fit_predict_n1' or len(want['fit_scale']) == N)
+
+
+def test_the_layout_of_the_yielded_tuples():
+    """_fit yields (idxs, Nidx, results); results holds seven arrays where the likelihood was asked for the scale, else five
+    (pdf.logprob's own rule), and with a foreign lprob_func it is the very tuple the user's function returned"""
+    from frankenz_amd import pdf as fpdf
+    g = load_golden('g14_network_inference')
+    fixed = make_net(g, track_scale=False, lpnet_kwargs={'free_scale': False, 'ignore_model_err': True})
+    cases = [(make_net(g), dict(lprob_kwargs={'free_scale': True, 'return_scale': True}), 7),
+             (make_net(g), dict(), 5),
+             (make_net(g), dict(nodes_only=True), 7),
+             (fixed, dict(nodes_only=True), 5)]
+    for net, kw, want in cases:
+        with np.errstate(all='ignore'):
+            res = list(net._fit(*g14_objects(g), **kw))
+        assert len(res) == len(g['data'])
+        for idxs, m, r in res:
+            assert len(r) == want and len(idxs) == m and all(len(a) == m for a in r)
+    made = []
+
+    def mine(*a, **k):
+        made.append(fpdf.logprob(*a, **k))
+        return made[-1]
+    with np.errstate(all='ignore'):
+        res = list(make_net(g)._fit(*g14_objects(g), lprob_func=mine))
+    assert len(res) == len(made) == len(g['data'])
+    for r, m in zip(res, made):
+        assert len(r) == 3 and r[2] is m
+
+
+def test_save_fits_false_leaves_the_network_as_it_was():
+    g = load_golden('g14_network_inference')
+    d, _ = dicts()
+    net = make_net(g)
+    with np.errstate(all='ignore'):
+        res = list(net._fit_predict(*g14_objects(g), g['labels'], g['label_errs'], label_dict=d, save_fits=False))
+    assert len(res) == len(g['data'])
+    assert net.neighbors is None and net.Nneighbors is None
+    for k in FIT_LISTS[1:]:
+        assert getattr(net, k) is None, k
+
+
+def test_a_foreign_lprob_func_on_a_label_grid_matches_the_device_path():
+    """the union path with the user's likelihood: the PDFs come from knn_predict_logwt on the ln-posteriors it returned"""
+    from frankenz_amd import pdf as fpdf
+    g = load_golden('g14_network_inference')
+    d, _ = dicts()
+    mine = lambda *a, **k: fpdf.logprob(*a, **k)
+    net, net2 = make_net(g), make_net(g)
+    args = g14_objects(g) + (g['labels'], g['label_errs'])
+    with np.errstate(all='ignore'):
+        p0, (lm0, le0) = net.fit_predict(*[np.copy(a) for a in args], label_grid=d.grid, return_gof=True, verbose=False)
+        p1, (lm1, le1) = net2.fit_predict(*[np.copy(a) for a in args], label_grid=d.grid, lprob_func=mine, return_gof=True, verbose=False)
+    eq(p0, p1, rtol=1e-9, atol=1e-14)
+    eq(lm0, lm1); eq(le0, le1)
+    np.testing.assert_array_equal(cat(net.neighbors, 'int'), cat(net2.neighbors, 'int'))
+
+
 def test_a_larger_network_against_the_oracle():
     """2 000 models on 60 nodes, 300 objects (more than one wave's worth of nodes, unions of hundreds of models)"""
     from frankenz_amd.networks import Network
