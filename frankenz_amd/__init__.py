@@ -8,7 +8,7 @@ C ABI in ``include/frankenz_hip.h`` (``libfrankenz_hip.so``, loaded with ctypes)
 There is no CPU fallback: importing the engine without the built library raises.
 """
 from .pdf import (PDFDict, gaussian, gaussian_bin, gauss_kde, gauss_kde_dict, loglike, logprob, logprob_prior,
-                  logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize, sample_labels)
+                  logprob_prior_lerp, luptitude, magnitude, pdfs_resample, pdfs_summarize, posterior_scores, sample_labels)
 from .bruteforce import BruteForce
 from .knn import NearestNeighbors
 from .samplers import model_weight_em, model_weight_sampler
@@ -18,4 +18,4 @@ from . import calibrate, fitting, networks, pdf, plotting, priors, reddening, sa
 __version__ = "0.1.0"
 __all__ = ["BruteForce", "NearestNeighbors", "PDFDict", "gaussian", "gaussian_bin", "gauss_kde",
            "gauss_kde_dict", "loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "luptitude", "magnitude",
-           "pdfs_resample", "pdfs_summarize", "sample_labels", "model_weight_sampler", "model_weight_em", "SparseFits", "calibrate", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]
+           "pdfs_resample", "pdfs_summarize", "posterior_scores", "sample_labels", "model_weight_sampler", "model_weight_em", "SparseFits", "calibrate", "fitting", "networks", "pdf", "plotting", "priors", "reddening", "samplers", "simulate"]

@@ -154,6 +154,7 @@ ABI = {
     "fz_row_bins": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _F64, _I32, _P, _P, _P, _P]),
     "fz_row_cdf": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I32, _F64, _P, _P]),
     "fz_row_quantiles": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _F64, _P, _P, _P, _P]),
+    "fz_row_scores": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I32, _F64, _P, _P, _P, _P, _P, _P]),
     "fz_fit_sparse": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(LikeOpts), C.POINTER(PriorLerp), _I64, _F64] + [_P] * 12),
     "fz_knn_draw_features": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(KnnMap), C.c_uint32, C.c_uint32, _I64, _P]),
     "fz_knn_draw_trees": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, C.POINTER(KnnMap), C.c_uint32, C.c_uint32, _P]),

@@ -26,6 +26,7 @@
 #include "fz_moments.h"
 #include "fz_bins.h"
 #include "fz_quantile.h"
+#include "fz_scores.h"
 
 using namespace fz;
 
@@ -1272,6 +1273,7 @@ extern "C" int fz_predict_logwt(fz_ctx* c, const double* logwt, int64_t N, int32
 #include "fz_moments_host.inc"
 #include "fz_bins_host.inc"
 #include "fz_quantile_host.inc"
+#include "fz_scores_host.inc"
 
 #ifdef FZ_KM_STATS
 extern "C" int fz_debug_kmstats(unsigned long long* out, int reset) {

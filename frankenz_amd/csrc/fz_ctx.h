@@ -148,6 +148,8 @@ struct fz_ctx {
     DevBuf d_mom[9];
     // posterior bin masses and CDFs (fz_bins_host.inc, which lists them)
     DevBuf d_bins[8];
+    // posterior scoring rules (fz_scores_host.inc, which lists them beside the d_bins it shares)
+    DevBuf d_scores[4];
 
     std::vector<DevBuf*> all_bufs() {
         std::vector<DevBuf*> v = {&d_y, &d_ye2, &d_ye, &d_rec0, &d_rec1, &d_ye2c, &d_mbits, &d_lgA, &d_lgB, &d_widths, &d_offsets, &d_kern, &d_pos,
@@ -163,6 +165,7 @@ struct fz_ctx {
         for (auto& b : d_sparse) v.push_back(&b);
         for (auto& b : d_mom) v.push_back(&b);
         for (auto& b : d_bins) v.push_back(&b);
+        for (auto& b : d_scores) v.push_back(&b);
         return v;
     }
 };

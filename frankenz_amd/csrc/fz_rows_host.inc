@@ -77,13 +77,14 @@ struct RowsIn {
     const int64_t* nnb() const { return cv.as<const int64_t>(); }
 };
 // Objects [0, N) in chunks under the workspace limit: the bytes per object are those of the stages a host caller's rows go through
-// (none: one chunk).  Per chunk every stage's view is formed (StageRows::as), body(i0, n) runs and the staged outputs go back.
+// and of the per-object scratch a site names (a NULL argument with `scratch`); none: one chunk.  Per chunk every stage's view is
+// formed (StageRows::as), body(i0, n) runs and the staged outputs go back.
 template <class Body>
 int for_row_chunks(fz_ctx* c, int64_t N, RowsIn& in, std::initializer_list<StageRows*> more, Body&& body) {
     std::vector<StageRows*> stages{&in.rv, &in.nv, &in.cv};
     stages.insert(stages.end(), more.begin(), more.end());
     int64_t per_obj = 0;
-    for (const StageRows* s : stages) if (s->staged()) per_obj += (int64_t)s->row;
+    for (const StageRows* s : stages) if (s->staged() || (s->scratch && !s->dev)) per_obj += (int64_t)s->row;
     int64_t nc = per_obj ? std::min<int64_t>(std::max<int64_t>(1, c->ws_limit / per_obj), 1 << 18) : N;
     nc = std::max<int64_t>(1, std::min(nc, N));
     for (int64_t i0 = 0; i0 < N; i0 += nc) {

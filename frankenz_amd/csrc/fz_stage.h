@@ -7,7 +7,8 @@
 enum StageDir { STAGE_IN = 1, STAGE_OUT = 2, STAGE_INOUT = 3 };
 
 // Rows [i0, i0 + n) of an argument, chunk by chunk.  The pointer's kind is asked for once, here.  A NULL argument gives a NULL view,
-// or with `scratch` the named buffer (an optional output that the kernel writes all the same).
+// or with `scratch` the named buffer (an optional output that the kernel writes all the same).  Under for_row_chunks
+// (fz_rows_host.inc) such a buffer counts towards the bytes per object: a call with one is chunked even when every array is on the device.
 struct StageRows {
     fz_ctx* c = nullptr; char* host = nullptr; size_t row = 0; DevBuf* buf = nullptr; int dir = 0; bool dev = false, scratch = false;
     StageRows() = default;

@@ -435,6 +435,17 @@ class Engine(object):
                                         ptr(probs), int(Q), float(lncut), ptr(out), ptr(cnt[0:1]), ptr(cnt[1:2]), ptr(cnt[2:3])))
         return int(cnt[0]), int(cnt[1]), int(cnt[2])
 
+    def row_scores(self, rows, n, W, M, labels, label_errs, points, P, per_object=False, lncut=-np.inf, lnpdf=None, crps=None, spread=None,
+                   sqnorm=None, ninc=None, neighbors=None, nnbr=None):
+        """fz_row_scores (docs/scores.md): the scoring rules of every row's mixture at ``points`` (P) or, with ``per_object``, (n, P) ->
+        whichever of ``lnpdf`` (n, P), ``crps`` (n, P), ``spread`` (n), ``sqnorm`` (n) and ``ninc`` (n) int64 are given; returns the
+        number of rows without a posterior"""
+        ns = np.zeros(1, dtype=np.int64)
+        check(self.lib.fz_row_scores(self.h, ptr(rows), int(n), int(W), ptr(neighbors), ptr(nnbr), int(M), ptr(labels), ptr(label_errs),
+                                     ptr(points), int(P), int(bool(per_object)), float(lncut), ptr(lnpdf), ptr(crps), ptr(spread),
+                                     ptr(sqnorm), ptr(ninc), ptr(ns)))
+        return int(ns[0])
+
     def phot_sums(self, x, xe, xm, mean, var, n, B, clip=0.):
         """fz_phot_sums -> (sums (3, B) float64 = A, B, C; counts (2, B) int64 = n, nclip)"""
         sums, counts = np.zeros((3, int(B))), np.zeros((2, int(B)), dtype=np.int64)

@@ -18,7 +18,8 @@ from .engine import HostObjects, get_engine, kde_opts, like_opts
 
 __all__ = ["loglike", "logprob", "logprob_prior", "logprob_prior_lerp", "lerp_cells", "gaussian", "gauss_kde", "gauss_kde_dict",
            "magnitude", "luptitude", "PDFDict", "pdfs_summarize", "pdfs_resample", "sample_labels", "sparsify_logwt", "posterior_moments",
-           "gaussian_bin", "posterior_bins", "posterior_cdf", "posterior_quantiles", "BINS_MAX"]
+           "gaussian_bin", "posterior_bins", "posterior_cdf", "posterior_quantiles", "posterior_scores", "BINS_MAX",
+           "SCORES_NMAX"]
 
 BINS_MAX = 256       # FZ_BINS_MAX: bins of a posterior_bins call, points of a posterior_cdf call
 
@@ -368,17 +369,12 @@ def posterior_bins(logwt, labels, label_errs, bins, neighbors=None, Nneighbors=N
     return (out, (below, above)) if return_outside else out
 
 
-def posterior_cdf(logwt, labels, label_errs, points, neighbors=None, Nneighbors=None, wt_thresh=1e-3, device=None):
-    """The mixture CDF P(label <= x | data) of the same kernel, selection and normalisation as ``posterior_bins`` (extension;
-    docs/bins.md).  ``points``: ``(Ndata, P)`` per object, ``(1, P)`` or ``(P,)`` shared by all objects -- ``P <= 256``, finite, in
-    any order -- giving ``(Ndata, P)``; or ``(Ndata,)``, one point per object, giving ``(Ndata,)``: with the true labels of a
-    validation sample that is its PIT.  (A 1-D array of exactly ``Ndata`` points is read as one per object; pass ``(1, P)`` to share
-    it.)"""
-    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+def _cdf_points(points, N):
+    """the `points` conventions `posterior_cdf` and `posterior_scores` share -> x, P, per_object, one (a point per object)"""
     x = _rows_arg(points, np.float64, "points")
     shape = tuple(int(v) for v in x.shape)
-    pit = len(shape) == 1 and shape[0] == N
-    if pit:
+    one = len(shape) == 1 and shape[0] == N
+    if one:
         P, per_object = 1, True
     elif len(shape) == 1 or (len(shape) == 2 and shape[0] == 1 and N != 1):
         P, per_object = shape[-1], False
@@ -392,6 +388,17 @@ def posterior_cdf(logwt, labels, label_errs, points, neighbors=None, Nneighbors=
         raise NotImplementedError("%d points, the limit is %d (FZ_BINS_MAX)" % (P, BINS_MAX))
     if isinstance(x, np.ndarray) and not np.isfinite(x).all():
         raise ValueError("`points` must be finite")
+    return x, P, per_object, one
+
+
+def posterior_cdf(logwt, labels, label_errs, points, neighbors=None, Nneighbors=None, wt_thresh=1e-3, device=None):
+    """The mixture CDF P(label <= x | data) of the same kernel, selection and normalisation as ``posterior_bins`` (extension;
+    docs/bins.md).  ``points``: ``(Ndata, P)`` per object, ``(1, P)`` or ``(P,)`` shared by all objects -- ``P <= 256``, finite, in
+    any order -- giving ``(Ndata, P)``; or ``(Ndata,)``, one point per object, giving ``(Ndata,)``: with the true labels of a
+    validation sample that is its PIT.  (A 1-D array of exactly ``Ndata`` points is read as one per object; pass ``(1, P)`` to share
+    it.)"""
+    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+    x, P, per_object, pit = _cdf_points(points, N)
     cdf = np.full((N, P), np.nan)
     get_engine(device).row_cdf(lw, N, W, M, y, s, x, P, cdf, per_object=per_object, lncut=lncut, neighbors=nb, nnbr=nn)
     return cdf[:, 0] if pit else cdf
@@ -437,6 +444,44 @@ def posterior_quantiles(logwt, labels, label_errs, q, neighbors=None, Nneighbors
                       RuntimeWarning, stacklevel=2)
     res = out[:, 0] if (one and isinstance(out, np.ndarray)) else out
     return (res, dict(nskip=nskip, nfail=nfail, niter=niter)) if return_info else res
+
+
+SCORES_NMAX = 16384  # FZ_SCORES_NMAX: included entries of a row whose pair sums (crps, spread, sqnorm) are asked for
+_SCORES = ('lnpdf', 'crps', 'spread', 'sqnorm', 'ninc')
+
+
+def posterior_scores(logwt, labels, label_errs, points, neighbors=None, Nneighbors=None, wt_thresh=1e-3, want=('lnpdf', 'crps', 'sqnorm'),
+                     return_info=False, device=None):
+    """Scoring rules of the mixture ``posterior_cdf`` evaluates, in closed form and without a grid (extension; docs/scores.md states
+    the law): under the selection and normalisation of ``posterior_bins``, per row and point ``x``
+
+    * ``lnpdf``  the ln-density at ``x`` (the log score), formed in ln space;
+    * ``crps``   the continuous ranked probability score ``E|X - x| - E|X - X'| / 2``;
+    * ``spread`` its second term ``E|X - X'| / 2``, per row;
+    * ``sqnorm`` the integral of the squared density, per row (the CDE loss is ``sqnorm - 2 exp(lnpdf)``);
+    * ``ninc``   the number of included entries, per row (int64).
+
+    ``points`` as in ``posterior_cdf``: ``(Ndata, P)``, ``(1, P)`` or ``(P,)`` with ``P <= 256``, or ``(Ndata,)``, one point per
+    object -- the true labels of a validation sample -- giving ``(Ndata,)`` for ``lnpdf`` and ``crps``.  ``labels`` and ``points``
+    must be finite, ``label_errs`` finite and not negative; 0 is a point mass (``sqnorm`` is then ``inf``, ``lnpdf`` ``inf`` at the
+    label itself).  ``want`` names the results to form; ``crps``, ``spread`` and ``sqnorm`` sum over all pairs of a row's included
+    entries, and a row with more than 16384 of them (``SCORES_NMAX``) is refused with ``NotImplementedError``.  Returns a dict of
+    arrays, with ``return_info`` also a dict with ``nskip`` (rows without a posterior: nan)."""
+    lw, y, s, nb, nn, N, W, M, lncut = _bins_rows(logwt, labels, label_errs, neighbors, Nneighbors, wt_thresh)
+    x, P, per_object, one = _cdf_points(points, N)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _SCORES for k in want):
+        raise ValueError("`want` names results among %s (got %r)" % (", ".join(_SCORES), want))
+    if isinstance(y, np.ndarray) and not np.isfinite(y).all():
+        raise ValueError("`labels` must be finite")
+    if isinstance(s, np.ndarray) and not (np.isfinite(s) & (s >= 0.)).all():
+        raise ValueError("`label_errs` must be finite and not negative (a flat kernel, inf, has no finite score)")
+    out = {k: (np.zeros(N, dtype=np.int64) if k == 'ninc' else np.full((N, P) if k in ('lnpdf', 'crps') else N, np.nan))
+           for k in _SCORES if k in want}
+    nskip = get_engine(device).row_scores(lw, N, W, M, y, s, x, P, per_object=per_object, lncut=lncut, neighbors=nb, nnbr=nn, **out)
+    if one:
+        out = {k: (v[:, 0] if k in ('lnpdf', 'crps') else v) for k, v in out.items()}
+    return (out, dict(nskip=nskip)) if return_info else out
 
 
 class PDFDict(object):

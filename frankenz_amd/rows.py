@@ -101,6 +101,16 @@ class RowConsumers(object):
         return posterior_quantiles(lw, model_labels, model_label_errs, q, neighbors=nb, Nneighbors=nn, wt_thresh=wt_thresh, out=out,
                                    device=self._device)
 
+    def predict_scores(self, model_labels, model_label_errs, points, logwt=None, wt_thresh=1e-3, want=('lnpdf', 'crps', 'sqnorm')):
+        """Extension (docs/scores.md): the scoring rules of that mixture at ``points`` in closed form (``pdf.posterior_scores``): with
+        the true labels of a validation sample, ``(Ndata,)``, the log score ``lnpdf``, the ``crps`` and the squared norm ``sqnorm``
+        of the CDE loss per object, as a dict; ``want`` may also name ``spread`` and ``ninc``."""
+        from .pdf import posterior_scores
+        self._check_labels(model_labels)
+        lw, nb, nn = self._row_source(logwt)
+        return posterior_scores(lw, model_labels, model_label_errs, points, neighbors=nb, Nneighbors=nn, wt_thresh=wt_thresh, want=want,
+                                device=self._device)
+
     def _predict_phot(self, models, models_err, models_mask, logwt):
         from .pdf import posterior_moments
         lw, nb, nn = self._row_source(logwt)

@@ -706,6 +706,45 @@ int  fz_row_quantiles(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, con
                       const double* labels, const double* label_errs, const double* probs, int64_t Q, double lncut, double* out,
                       int64_t* nskip, int64_t* nfail, int64_t* niter);
 
+/* ---- posterior scoring rules of the same label kernel (extension, no reference counterpart; docs/scores.md) ----
+ * The law.  Selection, m, w_t = exp(r_t - m), Z, the strict ln-space cut and the rows without a posterior (every output nan, ninc 0,
+ * counted in nskip) are those of fz_row_bins; entries past nnbr[i] are never read; repeated model indices are separate entries.
+ * Labels y must be finite, label errors s finite and >= 0 (s = inf, a flat kernel, has no finite score); an error whose square is 0
+ * in fp64 (s < 2^-537 = 2.2e-162) is read as s = 0, a point mass, everywhere below.  Points x (P) shared or
+ * (N, P) per object, finite, in any order, 1 <= P <= 256 (FZ_BINS_MAX).  With W_t = w_t / Z over the included entries,
+ *     A(d, v) = d erf(d / sqrt(2 v)) + sqrt(2 v / pi) exp(-d^2 / 2 v)      v > 0;   |d| for v == 0        (always >= 0)
+ *     G(d, v) = exp(-d^2 / 2 v) / sqrt(2 pi v)                             v > 0;   +inf if d == 0 else 0 for v == 0
+ *     lnpdf_ip = ln sum_t W_t N(x_ip | y_t, s_t)     formed in ln space: a_t = (r_t - m) - z_t^2 - ln s_t, z_t = (x - y_t) q_t,
+ *                q_t = 1 / (s_t sqrt 2); the max a_max of the a_t first, then a_max + ln sum exp(a_t - a_max) - ln Z - ln sqrt(2 pi).
+ *                An included entry with s_t == 0 contributes +inf if x == y_t, nothing otherwise.
+ *     crps_ip  = sum_t W_t A(x_ip - y_t, s_t^2)  -  spread_i
+ *     spread_i = 1/2 sum_t sum_u W_t W_u A(y_t - y_u, s_t^2 + s_u^2)  =  sum_{t<u} ... + 1/2 sum_t W_t^2 A(0, 2 s_t^2)
+ *     sqnorm_i = sum_t sum_u W_t W_u G(y_t - y_u, s_t^2 + s_u^2)       the integral of the squared density; +inf as soon as one
+ *                included s_t == 0
+ *     ninc_i   = the number of included entries
+ * (the CDE loss of a truth x is sqnorm - 2 exp(lnpdf)).  Each unordered pair is evaluated once and A and G share their exp; the pair
+ * sums are formed over w_t w_u and divided by Z twice.  Every sum has one fixed order that depends on the row alone.  Point sums: thread
+ * q of the object's 64 or 256 adds the entries q, q + 64 [256], ... in order, one xor butterfly over the lanes, the wave sums in wave
+ * order.  Pair sums: the included entries are compacted in entry order; tile I holds entries 64 I .. 64 I + 63 one per lane; a lane adds
+ * its terms over the tiles J >= I and the entries u of J in order (on the diagonal tile u > lane, and half of its own term), one
+ * butterfly; rows longer than FZ_DRAW_WAVE_LMAX deal the tiles I to four waves round-robin and add the wave sums in wave order.  The
+ * same bits whatever the chunking under the workspace limit, the object order, the number of objects in the call, the outputs asked
+ * for, and host or device arguments.
+ * The pair sums of a row are quadratic in its included count: with crps, spread or sqnorm asked for, a row of more than
+ * FZ_SCORES_NMAX = 16384 included entries is refused, -5, naming the object and the limit, after the counts of its chunk are known and
+ * before any pair sum of that chunk is started.  Without them there is no cap.
+ * Refusals, before any row is walked: P < 1, a point that is not finite, a label that is not finite or an error that is negative, nan
+ * or inf (the smallest such model is named), lncut >= 0 or nan: -4; P > 256 (FZ_BINS_MAX), W > 2^20 (FZ_DRAW_LMAX) or M >= 2^31: -5.
+ * An index outside [0, M) within the count, or a count outside [0, W]: -3, before anything is gathered for that row.
+ *
+ * fz_row_scores -- rows, neighbors, nnbr as fz_row_bins; labels, label_errs (M): host or device; points (P) with per_object == 0,
+ *   else (N, P) staged with the rows.  lnpdf, crps (N, P), spread, sqnorm (N), ninc (N) int64: host or device, staged in chunks, each
+ *   may be NULL; the pair sums run only if crps, spread or sqnorm is given.  Per object 24 W + 16 bytes of device scratch count towards
+ *   the chunk size under the workspace limit.  nskip: one int64. */
+int  fz_row_scores(fz_ctx* ctx, const double* rows, int64_t N, int64_t W, const int64_t* neighbors, const int64_t* nnbr, int64_t M,
+                   const double* labels, const double* label_errs, const double* points, int64_t P, int32_t per_object, double lncut,
+                   double* lnpdf, double* crps, double* spread, double* sqnorm, int64_t* ninc, int64_t* nskip);
+
 /* ---- Monte-Carlo draws of the k-NN fitter on the device (extension; docs/knn.md, knn.py:158-188 / 830-832) ----
  * The reference draws its K feature sets (knn.py:158-188) and every object's query features (knn.py:830-832) with NumPy's normal and
  * maps them to magnitudes / luptitudes.  Here the variates are Philox4x32-10: one call gives two standard normals by Box-Muller
